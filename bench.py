@@ -1,7 +1,14 @@
 """Headline benchmark: whole-node samples/s of the reference's SISA job on MNIST-scale data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...      (N > 1; one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  `--full` adds what
+the headline figure does not need: the link calibration before training (N > 1, `config.calib`)
+and the post-run self-check of the adopted server executor (`config.validated`,
+`config.validation`).  `--dump-outputs DIR` writes the trained state and the evaluation
+counters the last timed step left as DIR/<name>.npy (`_dump_outputs`); with the same arguments
+the data, the partition and the initial weights are the same in every run.
 
 Metric (BASELINE.json): "samples/sec (whole node) split-NN MNIST, world_size=2/3/5/9 on
 1/2/4/8 MI355X".  Config (BASELINE.json configs[3]): `split_nn.py --sisa
@@ -99,6 +106,52 @@ def _gathered_split(sess):
     return tot
 
 
+# --dump-outputs: arrays above this many elements are written as a fixed sample, so that the
+# whole dump stays well under 64 MB (model2_sisa's fc1 weight alone is 108 MB in fp32)
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_SAMPLE_SEED = 0
+
+
+def _flat_state(prefix, sd):
+    for k, v in sd.items():
+        if isinstance(v, dict):
+            yield from _flat_state(f"{prefix}.{k}", v)
+        else:
+            yield f"{prefix}.{k}", v
+
+
+def _dump_outputs(sess, out_dir):
+    """What a caller of the timed schedule receives once it has run, as it stands after the last
+    timed step: the state_dicts `--save_dir` would save (Bob's gathered from his TP shards: a
+    collective over the Bob ranks; each Alice's from the rank that hosts her) and the last
+    breakdown evaluation's counters.  One `<role>.<key>.npy` per tensor, float32 (counters:
+    float64).  A tensor of more than DUMP_MAX_ELEMS elements is written as the elements at
+    DUMP_MAX_ELEMS positions drawn once from a generator seeded by DUMP_SAMPLE_SEED and the
+    tensor's size (the same positions in every run and every build)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = []
+    if sess.is_bob:
+        sd = sess.tail.full_state_dict(sess.comm.tp_allgather)
+        if sess.rank == sess.pl.bob_root:
+            arrays += list(_flat_state("bob", sd))
+    for cid, al in sess.alices.items():
+        arrays += list(_flat_state(f"alice{cid}", sess._client_state(al)))
+    total = 0
+    for name, t in arrays:
+        v = t.detach().to("cpu", torch.float32).contiguous().reshape(-1).numpy()
+        if v.size > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([DUMP_SAMPLE_SEED, v.size])
+            v = v[np.sort(rng.integers(0, v.size, DUMP_MAX_ELEMS))]
+        else:
+            v = v.reshape(tuple(t.shape))
+        total += v.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    if sess.rank == 0 and getattr(sess, "last_eval", None) is not None:
+        np.save(os.path.join(out_dir, "last_eval.npy"), np.asarray(sess.last_eval, dtype=np.float64))
+    assert total <= 60_000_000, f"--dump-outputs wrote {total} bytes on rank {sess.rank}"
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -137,6 +190,13 @@ def main(argv=None):
     ap.add_argument("--python_epoch", action="store_true",
                     help="A/B: epochs as Python loops instead of the native executors")
     ap.add_argument("--json_out", type=str, default="")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the link calibration before "
+                         "training (N > 1; config.calib) and the post-run self-check of the server "
+                         "executor (config.validated / config.validation)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last step left to DIR/<name>.npy (float32 / "
+                         "float64): Bob's and every Alice's state_dict and the last evaluation's counters")
     ap.add_argument("--ranks_share_gpu", action="store_true",
                     help="rehearsal of the N > 1 path on a one-GPU box: every rank on cuda:0, gloo "
                          "control + host-staged data plane, Bob's TP all-reduce peer-mapped (RCCL "
@@ -144,6 +204,8 @@ def main(argv=None):
     ap.add_argument("--kernel_variant", action="append", default=[], metavar="SLOT=VALUE",
                     help="A/B hook: select a measured-alternative kernel form (_C.set_variant)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the timed steps)")
 
     from splitlearning_amd import ops
     from splitlearning_amd.config import parse_args
@@ -215,7 +277,7 @@ def main(argv=None):
         steps = [(n, f) for n, f in steps if n in ("local_training", "server_training")]
 
     calib = None
-    if N > 1:
+    if N > 1 and a.full:
         # measured link costs on this job's ranks and transport (not timed): the split modes'
         # per-batch act / cut-gradient message and Bob's TP all-reduce (parallel/calibrate.py)
         from splitlearning_amd.parallel.calibrate import measure
@@ -268,11 +330,16 @@ def main(argv=None):
         ref_t = sum(r["samples"] / rates[_phase_kind(sargs.mode, r["phase"])] for r in recs
                     if _phase_kind(sargs.mode, r["phase"]) is not None)
         base = samples / ref_t
-    # after the clock: is what the adopted server executor computed right?  (every rank joins;
-    # the persistent executor replays a slice against launch-per-stage from one snapshot, the
-    # replicated fc3 is compared across Bob ranks; the job's state is restored afterwards)
-    from splitlearning_amd.engine.resident import validate
-    val = validate(sess)
+    if a.dump_outputs:
+        _dump_outputs(sess, a.dump_outputs)
+    # --full, after the clock: is what the adopted server executor computed right?  (every rank
+    # joins; the persistent executor replays a slice against launch-per-stage from one snapshot,
+    # the replicated fc3 is compared across Bob ranks; the job's state is restored afterwards)
+    if a.full:
+        from splitlearning_amd.engine.resident import validate
+        val = validate(sess)
+    else:
+        val = {"validated": None, "reason": "the post-run self-check runs with --full"}
     sent = comm.gather_obj((comm.bytes_sent - b0) // max(1, a.steps), 0)
     sess._split_counts_all = comm.gather_obj(dict(getattr(sess, "native_split_epochs", {})), 0)
     if rank == 0:
@@ -314,8 +381,9 @@ def main(argv=None):
                 # a persistent epoch that failed mid-launch: rolled back, the job continued on
                 # launch-per-stage from that client epoch on ({from, epoch, reason}; None: none)
                 "server_executor_fallback": (getattr(sess, "resident_status", None) or {}).get("fallback"),
-                # the post-run self-check (engine/resident.validate): None = nothing to check
-                # for this mode; details: replayed steps, loss / fc3 gaps, fc3 replicas equal
+                # the post-run self-check (--full; engine/resident.validate): None = not run, or
+                # nothing to check for this mode; details: replayed steps, loss / fc3 gaps, fc3
+                # replicas equal
                 "validated": val.get("validated"),
                 "validation": val,
                 "calib": calib,

@@ -150,7 +150,7 @@ def test_bench_multi_rank_gloo(tmp_path, nranks):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", str(nranks), "--steps", "1", "--warmup", "1", "--num_samples", str(300 * nranks),
-           "--server_epochs", "1", "--json_out", str(out)]
+           "--server_epochs", "1", "--full", "--json_out", str(out)]
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="2")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -172,10 +172,45 @@ def test_bench_multi_rank_gloo(tmp_path, nranks):
         assert p in c["phase_seconds"], p
     # the SISA dump crossed ranks (Alices on ranks 1.. multicast to every Bob TP rank)
     assert sum(c["bytes_sent_per_rank_per_step"]) > 0
-    # self-calibration: the per-batch message cost to every peer and the TP all-reduce cost
+    # self-calibration (--full): the per-batch message cost to every peer and the TP all-reduce cost
     cal = c["calib"]
     assert cal["msg_us"] > 0 and sorted(cal["per_peer_us"]) == [str(r) for r in range(1, nranks)]
     assert cal["tp_allreduce_us"] > 0 and set(cal["bob_tp_policy"]) == {"vanilla", "ushape"}
+
+
+@pytest.mark.slow
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain bench.py run (no --full) skips the post-run self-check and says so, --steps sets
+    the number of timed steps, and --dump-outputs leaves the last step's state as float32 /
+    float64 .npy files of at most 64 MB in all: Bob's and Alice's state_dicts (tensors above
+    DUMP_MAX_ELEMS elements as a fixed sample) and the last evaluation's six counters."""
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
+           "--num_samples", "200", "--server_epochs", "1", "--dump-outputs", str(dump)]
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="2")
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 1 and rec["warmup"] == 0 and rec["ms_per_step"] > 0
+    assert rec["value"] == pytest.approx(rec["config"]["train_samples_per_step"] / (rec["ms_per_step"] / 1000), rel=1e-3)
+    assert rec["config"]["validated"] is None and "--full" in rec["config"]["validation"]["reason"]
+    assert rec["config"]["calib"] is None
+    got = {p.name[:-4]: np.load(p) for p in dump.iterdir()}
+    assert set(got) == {"alice1.conv_layers.0.weight", "alice1.conv_layers.0.bias", "last_eval"} | {
+        f"bob.fc{i}.{w}" for i in (1, 2, 3) for w in ("weight", "bias")}
+    assert sum(v.nbytes for v in got.values()) <= 64_000_000
+    for name, v in got.items():
+        assert v.dtype == (np.float64 if name == "last_eval" else np.float32), name
+        assert np.isfinite(v).all(), name
+    assert got["bob.fc3.weight"].shape == (100, 1000) and got["bob.fc1.bias"].shape == (5000,)
+    assert got["bob.fc1.weight"].shape == got["bob.fc2.weight"].shape == (1 << 22,)     # sampled
+    assert got["last_eval"].shape == (6,) and got["last_eval"][1] == 40                 # the 20 % test split
 
 
 @pytest.mark.slow
