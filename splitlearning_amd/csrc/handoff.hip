@@ -2,13 +2,16 @@
 // by word under uneven load (MI355X_MICROARCH.md: "test every hand-off under UNEVEN load,
 // consumer L1-warm, checking every word").
 //
-// Why: csrc/resident.hip, hybrid.hip and vanilla.hip hand tiles between workgroups inside one
+// Why: csrc/resident.hip, hybrid.hip, vanilla.hip and ushape.hip hand tiles between workgroups inside one
 // launch with the valid-forms table's row 1 (persist.h): the producer stores the payload
 // write-through (sc1), every wave drains (`s_waitcnt vmcnt(0)`), a workgroup barrier, then
 // ONE lane adds to a per-XCD counter shard (relaxed, agent scope); the consumer polls the
 // shards (relaxed agent loads = `sc1` loads), a workgroup barrier releases its waves, and
 // every load of the payload is an `sc1` buffer load (L1 bypassed).  This kernel runs exactly
-// that primitive (persist.h's own hst4 / hld4 / poll) in the harshest pattern the kernels
+// that primitive, the same functions resident.hip and vanilla.hip call (persist.h's arrive /
+// seam_wait and the sc1 store / load forms of hst4 / hld4; hybrid.hip and ushape.hip share its
+// spin and keep one piece each, the same code, in their own files), in the harshest pattern the
+// kernels
 // have: a payload REWRITTEN IN PLACE every round (as vanilla's fc1 tiles are between its
 // update and forward passes), consumers that re-read the same addresses every round (L1 and
 // L2 warm with the previous round's value), producers on every XCD, and per-round random
@@ -37,34 +40,12 @@ __device__ __forceinline__ uint32_t ho_val(uint32_t r, uint32_t src, uint32_t id
   return sl_fmix32((r * 0x9E3779B1u) ^ (src * 0x85EBCA77u) ^ (idx * 0xC2B2AE3Du));
 }
 
-__device__ __forceinline__ bool ho_wait(const HoArgs& a, int seam, unsigned tgt, int* s_ok) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    bool ok = true;
-    if (lane < 8) {
-      const unsigned* p = a.cnt + (seam * 8 + lane) * kHoStride;
-      if (poll(p) < tgt) {
-        const uint64_t t0 = wall_clock64();
-        while (poll(p) < tgt) {
-          if (failed(a.err)) {
-            ok = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-          if ((int64_t)(wall_clock64() - t0) > a.timeout) {
-            __hip_atomic_fetch_or(a.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = false;
-            break;
-          }
-        }
-      }
-    }
-    ok = __all(ok);
-    if (lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  return *s_ok != 0;
-}
+// counter of seam `seam`'s shard of producer w
+__device__ __forceinline__ int ho_shard(int seam, int w) { return seam * 8 + (w & 7); }
+// every shard of both seams receives the same G / 8 arrivals per round: seam_wait's per-shard
+// count is 1 and its multiplier carries rounds * G / 8 (this load and multiply are the 8
+// instructions per wait by which the kernel differs from its form before it shared seam_wait)
+__constant__ int ho_ones[16] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
 
 template <int MODE>
 __global__ void __launch_bounds__(kHoThreads) handoff_stress_kernel(HoArgs a) {
@@ -78,7 +59,8 @@ __global__ void __launch_bounds__(kHoThreads) handoff_stress_kernel(HoArgs a) {
   unsigned bad = 0;
   for (int r = 1; r <= a.R; ++r) {
     // the previous round's reads are done everywhere before this payload is rewritten
-    if (r > 1 && !ho_wait(a, 1, per * (unsigned)(r - 1), &s_ok)) break;
+    if (r > 1 && !seam_wait(a.err, a.timeout, a.cnt, kHoStride, 1, per * (unsigned)(r - 1), ho_ones, &s_ok))
+      break;
     // uneven load: a random delay, and on a random half of the workgroups a read-modify-write
     // stream over this workgroup's 64 KB of scratch (plain accesses: L2 / fabric pressure)
     const uint32_t hz = sl_fmix32((uint32_t)r * 0x27d4eb2du ^ (uint32_t)w * 0x165667b1u);
@@ -105,17 +87,22 @@ __global__ void __launch_bounds__(kHoThreads) handoff_stress_kernel(HoArgs a) {
       else
         __builtin_amdgcn_raw_buffer_store_b128(v, rD, off, 0, 0);
     }
-    // publish: every wave drains, barrier, one lane adds (MODE 3: behind an agent release)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      if (MODE == 3) {
+    // publish: the shipped arrive() (mode 1 differs only in its plain stores above).  Mode 3
+    // deviates on purpose, an agent release between the barrier and the add, and keeps this
+    // local form
+    if (MODE == 3) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_fetch_add(a.cnt + ho_shard(0, w) * kHoStride, 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
       }
-      __hip_atomic_fetch_add(a.cnt + (0 * 8 + (w & 7)) * kHoStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      arrive(a.cnt, kHoStride, ho_shard(0, w));
     }
-    if (!ho_wait(a, 0, per * (unsigned)r, &s_ok)) break;
+    if (!seam_wait(a.err, a.timeout, a.cnt, kHoStride, 0, per * (unsigned)r, ho_ones, &s_ok)) break;
     if (MODE == 3 || MODE == 4) {
       if (tid < 64) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -148,9 +135,7 @@ __global__ void __launch_bounds__(kHoThreads) handoff_stress_kernel(HoArgs a) {
         }
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(a.cnt + (1 * 8 + (w & 7)) * kHoStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    arrive(a.cnt, kHoStride, ho_shard(1, w));   // "reads done": the shipped form in every mode
     if (tid == 0) a.done[w] = (unsigned)r;
   }
   // per-workgroup mismatch count

@@ -58,6 +58,7 @@
 // cooperatively; nothing else may run on the device during the launch.
 #include "hybrid.h"
 #include "persist.h"
+#include "persist_launch.h"
 
 #include <string>
 
@@ -72,30 +73,12 @@ __device__ __forceinline__ int hy_seam(int seam, int shard) { return seam * 8 + 
 __device__ __forceinline__ int hy_P(int b) { return kHySeams * 8 + b; }
 __device__ __forceinline__ int hy_R(int rb) { return kHySeams * 8 + kHyMaxNC + rb; }
 
-// bounded wait until *p >= tgt (one lane); false when it gave up
-__device__ __forceinline__ bool hy_spin(const HyArgs& a, const unsigned* p, unsigned tgt) {
-  if (poll(p) >= tgt) return true;
-  const uint64_t t0 = wall_clock64();
-  while (poll(p) < tgt) {
-    if (failed(a.err)) return false;
-    __builtin_amdgcn_s_sleep(1);
-    if ((int64_t)(wall_clock64() - t0) > a.timeout) {
-      __hip_atomic_fetch_or(a.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-  }
-  return true;
-}
-
-// every wave drains its write-through stores; the barrier orders the drains before the add
-__device__ __forceinline__ void hy_arrive(const HyArgs& a, int idx) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(hy_cnt(a, idx), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the 8 shards of a seam (shard s receives shard_n[seam][s] arrivals per step)
-// (s_sn: a.shard_n staged in LDS at the start, so the poll's target costs no global round trip)
+// The 8 shards of a seam (shard s receives s_sn[seam][s] arrivals per step; s_sn: a.shard_n
+// staged in LDS): persist.h's seam_wait in this kernel's own form, on the shared spin().  Every
+// thread forms all 8 targets and the polling lane picks its own by a select chain.  Routed through
+// wait_lanes (with this chain or with seam_wait's lane-indexed read, with or without the
+// compiler barrier) the kernel's register allocation moves: 256 VGPRs and 2-20 spilled in the
+// Adam instantiations (docs/PERF.md, "Shared hand-off primitive refactor").
 __device__ __forceinline__ bool hy_seam_wait(const HyArgs& a, int seam, unsigned mult, int* s_ok, const int* s_sn) {
   int idx[8];
   unsigned tgt[8];
@@ -116,7 +99,7 @@ __device__ __forceinline__ bool hy_seam_wait(const HyArgs& a, int seam, unsigned
           id = idx[s];
           tg = tgt[s];
         }
-      if (tg > 0) ok = hy_spin(a, hy_cnt(a, id), tg);
+      if (tg > 0) ok = spin(a.err, a.timeout, hy_cnt(a, id), tg);
     }
     ok = __all(ok);
     if (lane == 0) *s_ok = ok ? 1 : 0;
@@ -547,7 +530,7 @@ __global__ void __launch_bounds__(kHyThreads) hybrid_epoch_kernel(HyArgs a) {
         // fault injection (tests): at step fault_step this wait cannot be met, times out (err 2)
         // and every other wait gives up, as a hand-off that never arrives would make them
         const unsigned tg = i == a.fault_step ? 0xffffffffu : (unsigned)(i + 1) * (unsigned)s_fns[lane];
-        ok = hy_spin(a, hy_cnt(a, hy_R(rb)), tg);
+        ok = spin(a.err, a.timeout, hy_cnt(a, hy_R(rb)), tg);
       }
       ok = __all(ok);
       if (lane == 0) *s_ok = ok ? 1 : 0;
@@ -606,7 +589,7 @@ __global__ void __launch_bounds__(kHyThreads) hybrid_epoch_kernel(HyArgs a) {
         if (n < WR) hst4(rHB, bFP + (((par * NC + tb) * N2 + r0 + n) * 16 + 4 * lq) * 4, acc);
       }
     }
-    hy_arrive(a, hy_seam(0, w & 7));
+    arrive(a.cnt, kHyStride, hy_seam(0, w & 7));
     HY_MARK(2);
 
     // ================= H: P2 of the head rows, h2, logit partials
@@ -685,7 +668,7 @@ __global__ void __launch_bounds__(kHyThreads) hybrid_epoch_kernel(HyArgs a) {
           }
         }
       }
-      hy_arrive(a, hy_seam(1, w & 7));
+      arrive(a.cnt, kHyStride, hy_seam(1, w & 7));
       HY_MARK(4);
     }
 
@@ -755,7 +738,7 @@ __global__ void __launch_bounds__(kHyThreads) hybrid_epoch_kernel(HyArgs a) {
         if (act) hst4(rHB, bDL + ((par * 16 + m) * C4 + 4 * c4) * 4, d);
         if (tid == 0) a.loss[(int64_t)i * M + m] = ign ? 0.f : mx + logf(se) - zl;
       }
-      hy_arrive(a, hy_seam(2, w & 7));
+      arrive(a.cnt, kHyStride, hy_seam(2, w & 7));
       HY_MARK(6);
     }
 
@@ -791,7 +774,7 @@ __global__ void __launch_bounds__(kHyThreads) hybrid_epoch_kernel(HyArgs a) {
       __syncthreads();
       if (threadIdx.x < 16 && (int)threadIdx.x < M)
         hst4(rHB, bDZ + ((par * 16 + threadIdx.x) * N2 + 4 * w) * 4, *reinterpret_cast<const f32x4*>(sdzh + threadIdx.x * 4));
-      hy_arrive(a, hy_seam(3, w & 7));
+      arrive(a.cnt, kHyStride, hy_seam(3, w & 7));
       HY_MARK(8);
       {
         HY_IDX();
@@ -863,7 +846,7 @@ __global__ void __launch_bounds__(kHyThreads) hybrid_epoch_kernel(HyArgs a) {
         }
       }
     }
-    hy_arrive(a, hy_P(tb));
+    arrive(a.cnt, kHyStride, hy_P(tb));
     HY_MARK(10);
     // the first fc1 tile's state in flight under W2's update and the dz1 wait
     if (nt > 0) load_state(t_begin, sp[0], sm[0], sv[0], true);
@@ -902,7 +885,7 @@ __global__ void __launch_bounds__(kHyThreads) hybrid_epoch_kernel(HyArgs a) {
         const int blo = hy_colblk((16 * rbA) >> 2, NC, Q4);
         const int bhi = hy_colblk((min(16 * (rbA + nruns), N1) - 1) >> 2, NC, Q4);
         bool ok = true;
-        if (blo + lane <= bhi) ok = hy_spin(a, hy_cnt(a, hy_P(blo + lane)), (unsigned)(i + 1) * kHyNR);
+        if (blo + lane <= bhi) ok = spin(a.err, a.timeout, hy_cnt(a, hy_P(blo + lane)), (unsigned)(i + 1) * kHyNR);
         ok = __all(ok);
         if (lane == 0) *s_ok = ok ? 1 : 0;
       }
@@ -1044,39 +1027,12 @@ std::string hybrid_check(const HyArgs& a) {
 }
 
 bool hybrid_fits(const HyArgs& a, int device, std::string* why) {
-  std::string s = hybrid_check(a);
-  if (s.empty()) {
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, device) != hipSuccess) {
-      s = "device properties";
-    } else {
-      const void* fn = hybrid_fn(a);
-      int nb = 0;
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHyLds);
-      if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kHyThreads, kHyLds);
-      if (e != hipSuccess || nb < 1) s = "occupancy";
-      else if ((int64_t)nb * pr.multiProcessorCount < a.G) s = "workgroups not co-resident";
-    }
-  }
-  if (why) *why = s;
-  return s.empty();
+  return persist::fits(hybrid_check(a), hybrid_fn(a), kHyThreads, kHyLds, a.G, device, why);
 }
 
 hipError_t hybrid_epoch_launch(const HyArgs& a, hipStream_t st) {
-  if (!hybrid_check(a).empty()) return hipErrorInvalidValue;
-  if (a.S <= 0) return hipSuccess;
-  const void* fn = hybrid_fn(a);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHyLds);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(a.cnt, 0, (size_t)kHyCounters * kHyStride * sizeof(unsigned), st);
-  if (e != hipSuccess) return e;
-  HyArgs arg = a;
-  if (!a.coop) {
-    void* params[] = {&arg};
-    return hipLaunchKernel(fn, dim3(a.G), dim3(kHyThreads), params, (size_t)kHyLds, st);
-  }
-  void* params[] = {&arg};
-  return hipLaunchCooperativeKernel(fn, dim3(a.G), dim3(kHyThreads), params, (unsigned)kHyLds, st);
+  return persist::launch(hybrid_check(a), hybrid_fn(a), kHyThreads, kHyLds, a.G,
+                         (size_t)kHyCounters * kHyStride * sizeof(unsigned), a, st);
 }
 
 }  // namespace sl

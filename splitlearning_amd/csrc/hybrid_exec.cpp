@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "host.h"
+#include "persist_host.h"
 #include "hybrid.h"
 
 namespace py = pybind11;
@@ -213,24 +213,17 @@ class HybridEpoch {
       TORCH_CHECK((int64_t)step_rows->size() == S && acts.size(0) == S * B_,
                   "step_rows: one row count per step, acts exactly S * B rows");
     std::vector<float> adam(4 * S, 0.f);
-    std::vector<int32_t> seeds(4 * S);
-    for (int64_t i = 0; i < S; ++i) {
-      const SlOpt o = sl::make_opt_raw(kind_, lr_, beta1_, beta2_, eps_, wd_, mom_, t + 1 + i, nullptr);
-      adam[4 * i] = o.step_size;
-      adam[4 * i + 1] = o.inv_bc2_sqrt;
+    sl::host::fill_adam(adam, 4, 0, t, [&](int64_t step) {
+      return sl::make_opt_raw(kind_, lr_, beta1_, beta2_, eps_, wd_, mom_, step, nullptr);
+    });
+    sl::host::fill_rows(adam, 4, 2, -1, [&](int64_t i) {
       const int64_t rows = step_rows.has_value() ? (*step_rows)[i] : B_;
       TORCH_CHECK(rows >= 1 && rows <= B_, "step_rows: 1 .. B rows per step");
-      adam[4 * i + 2] = (float)(1.0 / (double)rows);
-      const uint64_t s0 = sl::step_seed((uint64_t)seed_base, 0, (uint64_t)(fwd_count + 1 + i));
-      const uint64_t s1 = sl::step_seed((uint64_t)seed_base, 1, (uint64_t)(fwd_count + 1 + i));
-      seeds[4 * i] = (int32_t)(uint32_t)(s0 & 0xffffffffull);
-      seeds[4 * i + 1] = (int32_t)(uint32_t)(s0 >> 32);
-      seeds[4 * i + 2] = (int32_t)(uint32_t)(s1 & 0xffffffffull);
-      seeds[4 * i + 3] = (int32_t)(uint32_t)(s1 >> 32);
-    }
+      return rows;
+    });
     const at::Device dev = acts.device();
-    adam_ = at::from_blob(adam.data(), {4 * S}, at::TensorOptions().dtype(at::kFloat)).to(dev);
-    seeds_ = at::from_blob(seeds.data(), {4 * S}, at::TensorOptions().dtype(at::kInt)).to(dev);
+    adam_ = sl::host::upload(adam, dev);
+    seeds_ = sl::host::step_seeds(S, seed_base, fwd_count, dev);
     int64_t* tr = nullptr;
     int trs = 0;
     if (trace.has_value()) {
@@ -250,15 +243,8 @@ class HybridEpoch {
       tan = (int)(trace_all->numel() / (16LL * a_.G));
     }
     const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
-    // one clear of the error word per epoch; a chunk whose wait gave up leaves it set, and the
-    // host reads it before issuing the next chunk (one sync per chunk of thousands of steps), so
-    // no later chunk runs on a half-updated shard (the kernels only read the word inside a wait
-    // that is not already met, so they cannot be relied on to stop by themselves)
-    TORCH_CHECK(hipMemsetAsync(a_.err, 0, sizeof(int), st) == hipSuccess, "hybrid error word");
-    const int64_t cs = std::max<int64_t>(1, max_steps_);
-    for (int64_t s0 = 0; s0 < S; s0 += cs) {
-      if (s0 > 0 && err_.item<int>() != 0) break;
-      const int64_t n = std::min(cs, S - s0);
+    const int e = sl::host::run_chunks("hybrid", a_.err, err_, st, S, max_steps_, fault_step_,
+                                          [&](int64_t s0, int64_t n, int fault) {
       sl::HyArgs a = a_;
       a.S = (int)n;
       a.X = acts.data_ptr<float>() + s0 * B_ * a_.K1;
@@ -274,15 +260,13 @@ class HybridEpoch {
       a.tall = s0 == 0 ? ta : nullptr;
       a.tall_step = (int)trace_all_step;
       a.tall_n = s0 == 0 ? tan : 0;
-      a.fault_step = (fault_step_ >= s0 && fault_step_ < s0 + n) ? (int)(fault_step_ - s0) : -1;
+      a.fault_step = fault;
       const std::string why = sl::hybrid_check(a);
       TORCH_CHECK(why.empty(), "HybridEpoch: ", why);
       const hipError_t le = sl::hybrid_epoch_launch(a, st);
       TORCH_CHECK(le == hipSuccess, "hybrid epoch launch: ", hipGetErrorString(le));
-    }
+    });
     ++launches_;
-    if (fault_step_ >= 0) fault_step_ = -1;   // one injected fault per arming
-    const int e = err_.item<int>();   // one sync per client epoch
     TORCH_CHECK(e == 0, "hybrid server epoch: an in-launch wait gave up (error word ", e,
                 "; 2 = a hand-off timed out, 4 = the peer-mapped fc2 exchange failed)");
     return py::make_tuple(fwd_count + S, t + S, S * B_);

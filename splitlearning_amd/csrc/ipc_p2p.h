@@ -48,18 +48,19 @@ struct P2PMsg {
 };
 
 // The pair's regions and generations handed to a persistent kernel that sends and receives a
-// run of messages itself (csrc/vanilla.hip's remote-Alice epoch): send j of the run carries
+// run of messages itself (the remote-Alice epochs of csrc/vanilla.hip and ushape.hip, which
+// take it as a kernel argument): send j of the run carries
 // generation sgen0 + 1 + j, receive j rgen0 + 1 + j, each on the slot of its generation's parity
 struct P2PRun {
-  float* sdata[2];
-  uint32_t* sflag[2];
-  uint32_t* sack[2];
-  float* rdata[2];
-  uint32_t* rflag[2];
-  uint32_t* rack[2];
-  uint32_t sgen0, rgen0;
+  float* sdata[2];      // the peer's slot data[me][par]: what this side sends lands there
+  uint32_t* sflag[2];   // the peer's flag words [me][par][chunk]
+  uint32_t* sack[2];    // own ack words [peer][par][chunk] (the peer acks a message read)
+  float* rdata[2];      // own slot data[peer][par]: the peer's messages
+  uint32_t* rflag[2];   // own flag words [peer][par][chunk]
+  uint32_t* rack[2];    // the peer's ack words [me][par][chunk] (acks of its messages)
+  uint32_t sgen0, rgen0;   // the pair's generations before the run's first message
   int sprev[2];        // chunk counts of the messages two generations before sends 0 and 1
-  int* err;
+  int* err;            // the channel's error word (uncached) and its host-pinned mirror
   int* herr;
   int64_t timeout;
 };

@@ -1,9 +1,18 @@
-// Device helpers shared by the persistent server-epoch kernels (csrc/resident.hip,
-// csrc/hybrid.hip): hand-off loads / stores through buffer resources (write-through sc1
-// stores, L1-bypassing sc1 loads: MI355X_MICROARCH.md, the valid-forms table row 1), relaxed
-// counter polls, the dropout epilogue and the optimizer update with per-step scalars in VGPRs.
+// Device helpers shared by the four persistent one-launch epochs (csrc/resident.hip,
+// hybrid.hip, vanilla.hip, ushape.hip) and by the hand-off stress kernel (csrc/handoff.hip):
+// hand-off loads / stores through buffer resources (write-through sc1 stores, L1-bypassing sc1
+// loads: MI355X_MICROARCH.md, the valid-forms table row 1), the in-launch hand-off itself
+// (arrive / spin / wait_lanes / seam_wait / chan_wait), the dropout epilogue and the optimizer
+// update with per-step scalars in VGPRs.  Every counter wait of the four kernels is spin(), every
+// channel wait of the two remote-Alice instantiations (vanilla, U-shape) chan_wait(); resident,
+// vanilla and the stress kernel also run arrive / wait_lanes / seam_wait, so the stress test runs
+// what those ship.  Two call sites keep the same code in their own form because the
+// shared function moves their register allocation: hybrid.hip's hy_seam_wait and ushape.hip's
+// us_arrive (docs/PERF.md, "Shared hand-off primitive refactor").
 #pragma once
 #include "common.h"
+#include "ipc_ar.h"    // ipc_poll_flag, ipc_fail
+#include "ipc_p2p.h"   // P2PRun
 
 namespace sl {
 namespace persist {
@@ -32,6 +41,99 @@ __device__ __forceinline__ unsigned poll(const unsigned* p) {
 }
 __device__ __forceinline__ bool failed(const int* err) {
   return __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+}
+
+// ---- the in-launch hand-off -------------------------------------------------------------
+// Producer: write-through (sc1) payload stores, then arrive().  Consumer: wait_lanes() /
+// seam_wait(), then sc1 loads.  Every wait is bounded by wall clock: a timeout ORs its code
+// into the launch's error word `err` (2: a counter wait, 4: the channel), and a wait that finds
+// `err` already set gives up at once, so a stuck launch drains.
+// Rule for callers: err, timeout and cnt are references, and the argument must be the
+// kernel-argument field itself (a.err, a.timeout, a.cnt), never a local copy.  The field is
+// then loaded where it is used (inside the polling lane's branch, behind arrive's barrier); a
+// copy made ahead of the call is still correct but holds scalar registers across the phase,
+// which these kernels, at the 102-SGPR limit with hundreds of spills, pay for in moved code.
+// Nothing enforces this, and it holds for the compiler it was measured with: after a ROCm
+// upgrade, redo the instruction-stream comparison of docs/PERF.md.
+
+// One lane: bounded wait until the counter *p >= tgt; false when it gave up.
+__device__ __forceinline__ bool spin(int* const& err, const int64_t& timeout, const unsigned* p, unsigned tgt, int code = 2) {
+  if (poll(p) >= tgt) return true;
+  const uint64_t t0 = wall_clock64();
+  while (poll(p) < tgt) {
+    if (failed(err)) return false;
+    __builtin_amdgcn_s_sleep(1);
+    if ((int64_t)(wall_clock64() - t0) > timeout) {
+      __hip_atomic_fetch_or(err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return false;
+    }
+  }
+  return true;
+}
+
+// Publish this workgroup's hand-off stores on counter idx (word cnt[idx * stride]): every wave
+// drains its (write-through) stores, the barrier orders all the drains before thread 0's one
+// relaxed agent-scope add.
+// (ushape.hip's us_arrive is this body kept in that file: change both together.)
+__device__ __forceinline__ void arrive(unsigned* const& cnt, int stride, int idx) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt + idx * stride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Lanes [0, n) of wave 0 each wait for one counter word cnt[idx * stride]: tgt_of(lane, idx)
+// sets idx and returns the target (0: nothing to wait for).  The barrier then releases every
+// wave to its sc1 loads.  The result is uniform over the workgroup (false: a wait gave up).
+// (hybrid.hip's hy_seam_wait is this body, without the compiler barrier, kept in that file: change
+// both together.)
+template <typename F>
+__device__ __forceinline__ bool wait_lanes(int* const& err, const int64_t& timeout, unsigned* const& cnt, int stride, int n,
+                                           int* s_ok, F tgt_of) {
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    bool ok = true;
+    if (lane < n) {
+      int idx = 0;
+      const unsigned tg = tgt_of(lane, idx);
+      if (tg > 0) ok = spin(err, timeout, cnt + idx * stride, tg);
+    }
+    ok = __all(ok);
+    if (lane == 0) *s_ok = ok ? 1 : 0;
+  }
+  __syncthreads();
+  asm volatile("" ::: "memory");   // no load of the handed-off bytes is hoisted above the wait
+  return *s_ok != 0;
+}
+
+// The 8 per-XCD shards of `seam` (counter words cnt[(seam * 8 + shard) * stride]): shard s has
+// received mult * shard_n[seam * 8 + s] arrivals (shard_n in LDS or global memory; 0: the shard
+// has no producers).  mult = ~0u is the tests' "never met" wait: ~0u * n = 2^32 - n, which no
+// counter reaches.
+__device__ __forceinline__ bool seam_wait(int* const& err, const int64_t& timeout, unsigned* const& cnt, int stride, int seam,
+                                          unsigned mult, const int* shard_n, int* s_ok) {
+  return wait_lanes(err, timeout, cnt, stride, 8, s_ok, [&](int lane, int& idx) {
+    idx = seam * 8 + lane;
+    return mult * (unsigned)shard_n[idx];
+  });
+}
+
+// One lane: bounded wait until the flag / ack word *f of the peer-mapped channel lk reaches
+// generation `want` (a remote Alice, csrc/ipc_p2p.h); a timeout raises the launch's error word
+// (code 4) and the channel's.
+__device__ __forceinline__ bool chan_wait(int* const& err, const int64_t& timeout, const P2PRun& lk, const uint32_t* f,
+                                          uint32_t want) {
+  if ((int32_t)(ipc_poll_flag(f) - want) >= 0) return true;
+  const uint64_t t0 = wall_clock64();
+  while ((int32_t)(ipc_poll_flag(f) - want) < 0) {
+    if (failed(err)) return false;
+    __builtin_amdgcn_s_sleep(1);
+    if ((int64_t)(wall_clock64() - t0) > timeout) {
+      __hip_atomic_fetch_or(err, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ipc_fail(lk.err, lk.herr);
+      return false;
+    }
+  }
+  return true;
 }
 
 __device__ __forceinline__ float drop_relu(float v, uint32_t lo, uint32_t hi, uint32_t row, uint32_t col,

@@ -47,6 +47,7 @@
 // device's CUs during the launch (the SISA server phase runs no other stream on Bob's GPU).
 #include "resident.h"
 #include "persist.h"
+#include "persist_launch.h"
 
 #include <string>
 
@@ -56,54 +57,13 @@ namespace {
 
 using namespace persist;
 
-// Publish this workgroup's hand-off stores of `seam`: every wave drains its (write-through)
-// stores, the barrier orders all the drains before thread 0's counter add.
-__device__ __forceinline__ void arrive(unsigned* cnt, int seam, int w) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0)
-    __hip_atomic_fetch_add(cnt + (seam * 8 + (w & 7)) * kResShardStride, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-}
+// counter of seam `seam`'s shard of producer w (shard w % 8)
+__device__ __forceinline__ int res_shard(int seam, int w) { return seam * 8 + (w & 7); }
 
 // Row-block hand-off (fc1 look-ahead partials of one 16-row block's column groups to the
 // block's last-arriving group): one counter per row block after the seam shards.
 __device__ __forceinline__ unsigned* rb_counter(unsigned* cnt, int rb) {
   return cnt + (kResSeams * 8 + rb) * kResShardStride;
-}
-
-// Wait until every shard of `seam` holds `mult` arrivals per producer of that shard (lanes
-// 0..7 of wave 0 poll one shard each, relaxed, with s_sleep); the barrier then releases every
-// wave to its sc1 loads.  False (uniform over the workgroup) when the wait gave up.
-__device__ __forceinline__ bool seam_wait(const ResArgs& a, int seam, unsigned mult, int* s_ok) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    bool ok = true;
-    if (lane < 8) {
-      const int n = a.shard_n[seam * 8 + lane];
-      const unsigned* p = a.cnt + (seam * 8 + lane) * kResShardStride;
-      const unsigned tgt = mult == 0xffffffffu ? mult : mult * (unsigned)n;   // ~0u: never met
-      if (n > 0 && poll(p) < tgt) {
-        const uint64_t t0 = wall_clock64();
-        while (poll(p) < tgt) {
-          if (failed(a.err)) {
-            ok = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-          if ((int64_t)(wall_clock64() - t0) > a.timeout) {
-            __hip_atomic_fetch_or(a.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = false;
-            break;
-          }
-        }
-      }
-    }
-    ok = __all(ok);
-    if (lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  return *s_ok != 0;
 }
 
 // LDS carve (bytes; every offset a multiple of 16)
@@ -343,7 +303,7 @@ __global__ void __launch_bounds__(kResThreads) resident_epoch_kernel(ResArgs a) 
         hst1(rH1, ((par * 16 + m) * N1p + n) * 4, v);
       }
     }
-    arrive(a.cnt, 0, rb);            // seam A's shards count row blocks (rb % 8)
+    arrive(a.cnt, kResShardStride, res_shard(0, rb));            // seam A's shards count row blocks (rb % 8)
     return true;
   };
   // W2 after a step, in the fc1 tiles' layout W2B[par][rb(j)][w][j % 16][ii] (this workgroup's
@@ -388,7 +348,7 @@ __global__ void __launch_bounds__(kResThreads) resident_epoch_kernel(ResArgs a) 
     RES_MARK(0);
     // fault injection (tests): at step fault_step this wait cannot be met, times out (err 2) and
     // every other wait gives up, as a hand-off that never arrives would make them
-    if (!seam_wait(a, 0, i == a.fault_step ? 0xffffffffu : (unsigned)(i + 1), s_ok)) break;
+    if (!seam_wait(a.err, a.timeout, a.cnt, kResShardStride, 0, i == a.fault_step ? 0xffffffffu : (unsigned)(i + 1), a.shard_n, s_ok)) break;
     RES_MARK(1);
     {
       RES_IDX();
@@ -516,12 +476,12 @@ __global__ void __launch_bounds__(kResThreads) resident_epoch_kernel(ResArgs a) 
         }
       }
     }
-    arrive(a.cnt, 1, w);
+    arrive(a.cnt, kResShardStride, res_shard(1, w));
     RES_MARK(5);
 
     // ================= B: row m's logits, softmax-CE, dlogits (workgroups m < M)
     if (w < M) {
-      if (!seam_wait(a, 1, (unsigned)(i + 1), s_ok)) break;
+      if (!seam_wait(a.err, a.timeout, a.cnt, kResShardStride, 1, (unsigned)(i + 1), a.shard_n, s_ok)) break;
       RES_MARK(6);
       RES_IDX();
       const int m = w;
@@ -584,12 +544,12 @@ __global__ void __launch_bounds__(kResThreads) resident_epoch_kernel(ResArgs a) 
         if (act) hst4(rDL, ((par * 16 + m) * C4 + 4 * c4) * 4, d);
         if (tid == 0) a.loss[(int64_t)i * M + m] = ign ? 0.f : mx + logf(se) - zl;
       }
-      arrive(a.cnt, 2, w);
+      arrive(a.cnt, kResShardStride, res_shard(2, w));
       RES_MARK(7);
     }
 
     // ================= C: b3; dz2, W3 / b2 / W2 steps of this workgroup's fc2 rows
-    if (!seam_wait(a, 2, (unsigned)(i + 1), s_ok)) break;
+    if (!seam_wait(a.err, a.timeout, a.cnt, kResShardStride, 2, (unsigned)(i + 1), a.shard_n, s_ok)) break;
     RES_MARK(8);
     {
       RES_IDX();
@@ -626,7 +586,7 @@ __global__ void __launch_bounds__(kResThreads) resident_epoch_kernel(ResArgs a) 
       if (tid < M)   // DZ2[par][m][w][ii] = dz2[m][n = w + G ii]
         hst4(rDZ, (((par * 16 + tid) * G + w) * 4) * 4, *reinterpret_cast<const f32x4*>(sdz2 + tid * 4));
     }
-    arrive(a.cnt, 3, w);
+    arrive(a.cnt, kResShardStride, res_shard(3, w));
     RES_MARK(9);
     // the optimizer steps of b3, W3, b2 and W2 and W2_{t+1}'s publication (for the next step's
     // dz1) after the seam: only dz2 is on its critical path; they fill this workgroup's wait
@@ -682,7 +642,7 @@ __global__ void __launch_bounds__(kResThreads) resident_epoch_kernel(ResArgs a) 
       // one poll: issued behind W2_t's operand loads it waited for them, measured 4.3 us from
       // the publication to the release), then both operands load in one round trip.
       constexpr int KB = 256 / 4 / NW;                       // blocks per wave (G <= 256)
-      if (!seam_wait(a, 3, (unsigned)(i + 1), s_ok)) break;
+      if (!seam_wait(a.err, a.timeout, a.cnt, kResShardStride, 3, (unsigned)(i + 1), a.shard_n, s_ok)) break;
       RES_MARK(10);
       {
         RES_IDX();
@@ -841,56 +801,19 @@ static std::string check_shape(const ResArgs& a) {
   return "";
 }
 
+// the instantiation a launch uses (Adam or SGD-momentum): their register counts differ
+static const void* resident_fn(const ResArgs& a) {
+  return a.o.kind == 2 ? reinterpret_cast<const void*>(&resident_epoch_kernel<true>)
+                       : reinterpret_cast<const void*>(&resident_epoch_kernel<false>);
+}
+
 bool resident_fits(const ResArgs& a, int device, std::string* why) {
-  std::string s = check_shape(a);
-  if (s.empty()) {
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, device) != hipSuccess) {
-      s = "device properties";
-    } else {
-      // the instantiation that will be launched (Adam or SGD-momentum): their register counts differ
-      const void* fn = a.o.kind == 2 ? reinterpret_cast<const void*>(&resident_epoch_kernel<true>)
-                                     : reinterpret_cast<const void*>(&resident_epoch_kernel<false>);
-      int nb = 0;
-      const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kResThreads, kResLds);
-      if (e != hipSuccess || nb < 1) s = "occupancy";
-      else if ((int64_t)nb * pr.multiProcessorCount < a.G) s = "workgroups not co-resident";
-    }
-  }
-  if (why) *why = s;
-  return s.empty();
+  return persist::fits(check_shape(a), resident_fn(a), kResThreads, kResLds, a.G, device, why);
 }
 
 hipError_t resident_epoch_launch(const ResArgs& a, hipStream_t st) {
-  if (!check_shape(a).empty()) return hipErrorInvalidValue;
-  if (a.S <= 0) return hipSuccess;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&resident_epoch_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kResLds);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&resident_epoch_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kResLds);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  hipError_t e = hipMemsetAsync(a.cnt, 0, (size_t)kResCounters * kResShardStride * sizeof(unsigned), st);
-  if (e != hipSuccess) return e;
-  // cooperative: the runtime checks at launch time that all G workgroups fit at once (a
-  // plain launch of a grid that does not fit would park workgroups behind ones that spin on
-  // them); +15-19 us of host time per launch, once per client epoch (MI355X_MICROARCH.md)
-  const void* fn = a.o.kind == 2 ? reinterpret_cast<const void*>(&resident_epoch_kernel<true>)
-                                 : reinterpret_cast<const void*>(&resident_epoch_kernel<false>);
-  ResArgs arg = a;
-  if (!a.coop) {
-    if (a.o.kind == 2)
-      resident_epoch_kernel<true><<<a.G, kResThreads, kResLds, st>>>(a);
-    else
-      resident_epoch_kernel<false><<<a.G, kResThreads, kResLds, st>>>(a);
-    return hipGetLastError();
-  }
-  void* params[] = {&arg};
-  return hipLaunchCooperativeKernel(fn, dim3(a.G), dim3(kResThreads), params, (unsigned)kResLds, st);
+  return persist::launch(check_shape(a), resident_fn(a), kResThreads, kResLds, a.G,
+                         (size_t)kResCounters * kResShardStride * sizeof(unsigned), a, st);
 }
 
 }  // namespace sl

@@ -12,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "host.h"
+#include "persist_host.h"
 #include "resident.h"
 
 namespace py = pybind11;
@@ -184,24 +184,17 @@ class ResidentEpoch {
     // per-step tables: Adam {step_size, 1/sqrt(bc2)} at steps t+1 .. t+S and the two dropout
     // seeds at forward counts fwd_count+1 .. fwd_count+S
     std::vector<float> adam(4 * S, 0.f);
-    std::vector<int32_t> seeds(4 * S);
-    for (int64_t i = 0; i < S; ++i) {
-      const SlOpt o = sl::make_opt_raw(kind_, lr_, beta1_, beta2_, eps_, wd_, mom_, t + 1 + i, nullptr);
-      adam[4 * i] = o.step_size;
-      adam[4 * i + 1] = o.inv_bc2_sqrt;
+    sl::host::fill_adam(adam, 4, 0, t, [&](int64_t step) {
+      return sl::make_opt_raw(kind_, lr_, beta1_, beta2_, eps_, wd_, mom_, step, nullptr);
+    });
+    sl::host::fill_rows(adam, 4, 2, -1, [&](int64_t i) {
       const int64_t rows = step_rows.has_value() ? (*step_rows)[i] : B_;
       TORCH_CHECK(rows >= 1 && rows <= B_, "step_rows: 1 .. B rows per step");
-      adam[4 * i + 2] = (float)(1.0 / (double)rows);
-      const uint64_t s0 = sl::step_seed((uint64_t)seed_base, 0, (uint64_t)(fwd_count + 1 + i));
-      const uint64_t s1 = sl::step_seed((uint64_t)seed_base, 1, (uint64_t)(fwd_count + 1 + i));
-      seeds[4 * i] = (int32_t)(uint32_t)(s0 & 0xffffffffull);
-      seeds[4 * i + 1] = (int32_t)(uint32_t)(s0 >> 32);
-      seeds[4 * i + 2] = (int32_t)(uint32_t)(s1 & 0xffffffffull);
-      seeds[4 * i + 3] = (int32_t)(uint32_t)(s1 >> 32);
-    }
+      return rows;
+    });
     const at::Device dev = acts.device();
-    adam_ = at::from_blob(adam.data(), {4 * S}, at::TensorOptions().dtype(at::kFloat)).to(dev);
-    seeds_ = at::from_blob(seeds.data(), {4 * S}, at::TensorOptions().dtype(at::kInt)).to(dev);
+    adam_ = sl::host::upload(adam, dev);
+    seeds_ = sl::host::step_seeds(S, seed_base, fwd_count, dev);
     sl::ResArgs a = a_;
     a.S = (int)S;
     a.X = acts.data_ptr<float>();
@@ -221,14 +214,13 @@ class ResidentEpoch {
       a.trace_steps = (int)(trace->numel() / 32);
     }
     const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
-    // the executor's own error word starts clear on every launch: a wait that gave up in an
-    // earlier run (whose exception the caller handled) must not make this launch give up
-    TORCH_CHECK(hipMemsetAsync(a.err, 0, sizeof(int), st) == hipSuccess, "resident error word");
-    a.fault_step = fault_step_ < S ? (int)fault_step_ : -1;
-    fault_step_ = -1;                  // one injected fault per arming
-    const hipError_t le = sl::resident_epoch_launch(a, st);
-    TORCH_CHECK(le == hipSuccess, "resident epoch launch: ", hipGetErrorString(le));
-    const int e = err_.item<int>();   // one sync per client epoch
+    // one chunk of S steps: exactly one launch
+    const int e = sl::host::run_chunks("resident", a.err, err_, st, S, S, fault_step_,
+                                          [&](int64_t, int64_t, int fault) {
+      a.fault_step = fault;
+      const hipError_t le = sl::resident_epoch_launch(a, st);
+      TORCH_CHECK(le == hipSuccess, "resident epoch launch: ", hipGetErrorString(le));
+    });
     TORCH_CHECK(e == 0, "resident server epoch: an in-launch wait gave up (error word ", e,
                 "; 2 = a seam timed out, 4 = the peer-mapped fc2 exchange failed)");
     return py::make_tuple(fwd_count + S, t + S, S * B_);

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "common.h"
+#include "ipc_p2p.h"
 
 namespace sl {
 
@@ -32,20 +33,8 @@ constexpr int kUsCounters = 137;
 // run_alice, unchanged) and the launch speaks the peer-mapped channel (csrc/ipc_p2p.h) itself,
 // in run_bob's order: per step i it receives her activation (generation rgen0 + 1 + 2 i), sends
 // h2 (sgen0 + 1 + 2 i), receives her premasked dz2 (rgen0 + 2 + 2 i) and sends the cut gradient
-// (sgen0 + 2 + 2 i), each on the parity slot of its generation.
-struct UsLink {
-  float* sdata[2];          // her slot data[bob][par]
-  uint32_t* sflag[2];       // her flag words [bob][par][chunk]
-  const uint32_t* sack[2];  // own ack words [alice][par][chunk]
-  const float* rdata[2];    // own slot data[alice][par]
-  const uint32_t* rflag[2]; // own flag words [alice][par][chunk]
-  uint32_t* rack[2];        // her ack words [bob][par][chunk]
-  uint32_t sgen0, rgen0;
-  int sprev[2];             // chunk counts of the messages two generations before sends 0 (h2_0), 1 (dx_0)
-  int* err;
-  int* herr;
-};
-
+// (sgen0 + 2 + 2 i), each on the parity slot of its generation.  UsArgs::lk is the channel's own
+// P2PRun; channel waits are bounded by UsArgs::timeout, not by lk.timeout.
 struct UsArgs {
   // Bob: fc1 [N1][5408], fc2 [N2][N1], Adam moments of each
   float *W1, *m1, *v1, *b1, *mb1, *vb1;
@@ -81,7 +70,7 @@ struct UsArgs {
   // remote Alice: the <.., true> instantiation; RG row groups of 128 fc1 rows, G = 32 RG
   // workgroups (so a one-GPU test can leave CUs to her kernels); tabf [5] = the step's rows
   int rem, RG, G;
-  UsLink lk;
+  P2PRun lk;
 };
 
 std::string ushape_check(const UsArgs& a);

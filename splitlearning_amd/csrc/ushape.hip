@@ -66,6 +66,7 @@
 #include "ushape.h"
 #include "ipc_ar.h"
 #include "persist.h"
+#include "persist_launch.h"
 
 #include <string>
 
@@ -77,62 +78,12 @@ using namespace persist;
 
 __device__ __forceinline__ unsigned* us_cnt(const UsArgs& a, int i) { return a.cnt + i * kUsStride; }
 
-__device__ __forceinline__ bool us_spin(const UsArgs& a, const unsigned* p, unsigned tgt) {
-  if (poll(p) >= tgt) return true;
-  const uint64_t t0 = wall_clock64();
-  while (poll(p) < tgt) {
-    if (failed(a.err)) return false;
-    __builtin_amdgcn_s_sleep(1);
-    if ((int64_t)(wall_clock64() - t0) > a.timeout) {
-      __hip_atomic_fetch_or(a.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-  }
-  return true;
-}
-
-// every wave drains its write-through stores, the barrier orders the drains before lane 0's add
+// persist.h's arrive(), kept in this kernel's own form: through the shared function the remote
+// instantiations' register allocation moves (205 -> 217 VGPRs; docs/PERF.md)
 __device__ __forceinline__ void us_arrive(const UsArgs& a, int idx) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) __hip_atomic_fetch_add(us_cnt(a, idx), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// wave 0's lanes [0, n) wait for counters tgt_of(lane, idx); the barrier then releases every
-// wave to its sc1 loads.  Uniform result (false: a wait gave up)
-template <typename F>
-__device__ __forceinline__ bool us_wait(const UsArgs& a, int n, int* s_ok, F tgt_of) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    bool ok = true;
-    if (lane < n) {
-      int idx;
-      const unsigned tg = tgt_of(lane, idx);
-      if (tg > 0) ok = us_spin(a, us_cnt(a, idx), tg);
-    }
-    ok = __all(ok);
-    if (lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  asm volatile("" ::: "memory");
-  return *s_ok != 0;
-}
-
-// one lane: bounded wait until the channel flag / ack word *f reaches generation `want` (remote
-// Alice); a timeout raises the launch's error word and the channel's
-__device__ __forceinline__ bool us_pwait(const UsArgs& a, const uint32_t* f, uint32_t want) {
-  if ((int32_t)(ipc_poll_flag(f) - want) >= 0) return true;
-  const uint64_t t0 = wall_clock64();
-  while ((int32_t)(ipc_poll_flag(f) - want) < 0) {
-    if (failed(a.err)) return false;
-    __builtin_amdgcn_s_sleep(1);
-    if ((int64_t)(wall_clock64() - t0) > a.timeout) {
-      __hip_atomic_fetch_or(a.err, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ipc_fail(a.lk.err, a.lk.herr);
-      return false;
-    }
-  }
-  return true;
 }
 
 // arrivals per shard s of a seam whose producers are workgroups 0 .. n - 1 (shard w % 8)
@@ -353,7 +304,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
       bool ok = true;
       if (t < 16 / RG && m < Ms) {
         const int base = m * (kUsCh * kUsP) + cc * kUsP;
-        ok = us_pwait(a, a.lk.rflag[par] + ((lane & 1) ? base + kUsP - 1 : base) / kIpcChunk, gen);
+        ok = chan_wait(a.err, a.timeout, a.lk, a.lk.rflag[par] + ((lane & 1) ? base + kUsP - 1 : base) / kIpcChunk, gen);
       }
       ok = __all(ok);
       ipc_acquire();
@@ -376,7 +327,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
   auto send_chunk = [&](int c, uint32_t gen, int prev, int len, auto fill) -> bool {
     const int par = (int)(gen & 1u);
     if (threadIdx.x == 0) {
-      const bool ok = prev == 0 || us_pwait(a, a.lk.sack[par] + (c < prev ? c : 0), gen - 2u);
+      const bool ok = prev == 0 || chan_wait(a.err, a.timeout, a.lk, a.lk.sack[par] + (c < prev ? c : 0), gen - 2u);
       ipc_acquire();
       *s_ok = ok ? 1 : 0;
     }
@@ -412,7 +363,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
     const uint32_t pimg = (!REM && more) ? img_word(i + 1) : 0u;
 
     // ================= F: x_i of channel cc, the forward partial over its columns
-    if (!us_wait(a, 1, s_ok, [&](int, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 1, s_ok, [&](int, int& idx) {
           idx = kUsXC + cc;
           return i == a.fault_step ? 0xffffffffu : (unsigned)RG * (unsigned)(i + 1);
         }))
@@ -457,7 +408,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
     us_arrive(a, kUsPC + rg);
 
     // ================= R: h1 of my 4 rows, the fc2 partial over them
-    if (!us_wait(a, 1, s_ok, [&](int, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 1, s_ok, [&](int, int& idx) {
           idx = kUsPC + rg;
           return 32u * (unsigned)(i + 1);
         }))
@@ -498,7 +449,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
 
     // ================= H2: workgroup j = w < N2 reduces fc2 column j
     if (w < N2) {
-      if (!us_wait(a, 8, s_ok, [&](int l, int& idx) {
+      if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 8, s_ok, [&](int l, int& idx) {
             idx = kUsF2 + l;
             return (unsigned)(G / 8) * (unsigned)(i + 1);
           }))
@@ -553,7 +504,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
     if constexpr (REM) {
       const int len = rows_of(i) * N2;
       if (w < nchunks(len)) {
-        if (!us_wait(a, 8, s_ok, [&](int l, int& idx) {
+        if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 8, s_ok, [&](int l, int& idx) {
               idx = kUsL + l;
               return (unsigned)(i + 1) * us_shard_n(N2, l);
             }))
@@ -572,7 +523,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
     }
     // ================= CE: workgroup m = w < M: model3 logits of row m, softmax-CE, dlogits
     if (!REM && w < M) {
-      if (!us_wait(a, 8, s_ok, [&](int l, int& idx) {
+      if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 8, s_ok, [&](int l, int& idx) {
             idx = kUsL + l;
             return (unsigned)(i + 1) * us_shard_n(N2, l);
           }))
@@ -619,7 +570,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
       const uint32_t gen = a.lk.rgen0 + 2u + 2u * (uint32_t)i;
       if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
-        const bool ok = __all(lane < nchunks(len) ? us_pwait(a, a.lk.rflag[gen & 1u] + lane, gen) : true);
+        const bool ok = __all(lane < nchunks(len) ? chan_wait(a.err, a.timeout, a.lk, a.lk.rflag[gen & 1u] + lane, gen) : true);
         ipc_acquire();
         if (lane == 0) *s_ok = ok ? 1 : 0;
       }
@@ -633,7 +584,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
       }
       __syncthreads();
     } else {
-    if (!us_wait(a, 8, s_ok, [&](int l, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 8, s_ok, [&](int l, int& idx) {
           idx = kUsD + l;
           return (unsigned)(i + 1) * us_shard_n(M, l);
         }))
@@ -726,7 +677,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
     }
 
     // ================= X: the row group's dz1, the cut-gradient partial from the old W1
-    if (!us_wait(a, 1, s_ok, [&](int, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 1, s_ok, [&](int, int& idx) {
           idx = kUsDZ + rg;
           return 32u * (unsigned)(i + 1);
         }))
@@ -782,7 +733,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
       // ================= (remote) the cut gradient to her, her activation of batch i + 1 in
       const int len = rows_of(i) * (kUsCh * kUsP);
       if (w < nchunks(len)) {
-        if (!us_wait(a, kUsCh, s_ok, [&](int l, int& idx) {
+        if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, kUsCh, s_ok, [&](int l, int& idx) {
               idx = kUsDX + l;
               return (unsigned)RG * (unsigned)(i + 1);
             }))
@@ -812,7 +763,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
       }
     } else {
     // ================= C: conv job: backward, the channel's step, forward of batch i + 1
-    if (!us_wait(a, 1, s_ok, [&](int, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 1, s_ok, [&](int, int& idx) {
           idx = kUsDX + cc;
           return 8u * (unsigned)(i + 1);
         }))
@@ -859,7 +810,7 @@ __global__ void __launch_bounds__(kUsThreads) ushape_epoch_kernel(UsArgs a) {
       hst1(rHB, bCW + (((par * kUsCh + cc) * kUsRG + rg) * 16 + j) * 4, g);
     }
     us_arrive(a, kUsCW + cc);
-    if (!us_wait(a, 1, s_ok, [&](int, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 1, s_ok, [&](int, int& idx) {
           idx = kUsCW + cc;
           return 8u * (unsigned)(i + 1);
         }))
@@ -917,7 +868,7 @@ fin:
       const int s = a.S - 1;
       const uint32_t gd = a.lk.rgen0 + 2u + 2u * (uint32_t)s;
       const int nch = nchunks(rows_of(s) * N2);
-      if (w < nch && us_wait(a, 1, s_ok, [&](int, int& idx) {
+      if (w < nch && wait_lanes(a.err, a.timeout, a.cnt, kUsStride, 1, s_ok, [&](int, int& idx) {
             idx = kUsFin;
             return (unsigned)G;
           })) {
@@ -1016,37 +967,12 @@ static const void* us_kernel(const UsArgs& a) {
 }
 
 bool ushape_fits(const UsArgs& a, int device, std::string* why) {
-  std::string s = ushape_check(a);
-  if (s.empty()) {
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, device) != hipSuccess) {
-      s = "device properties";
-    } else {
-      const void* fn = us_kernel(a);
-      int nb = 0;
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kUsLds);
-      if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kUsThreads, kUsLds);
-      if (e != hipSuccess || nb < 1) s = "occupancy";
-      else if ((int64_t)nb * pr.multiProcessorCount < (a.rem ? a.G : kUsG)) s = "workgroups not co-resident";
-    }
-  }
-  if (why) *why = s;
-  return s.empty();
+  return persist::fits(ushape_check(a), us_kernel(a), kUsThreads, kUsLds, a.rem ? a.G : kUsG, device, why);
 }
 
 hipError_t ushape_epoch_launch(const UsArgs& a, hipStream_t st) {
-  if (!ushape_check(a).empty()) return hipErrorInvalidValue;
-  if (a.S <= 0) return hipSuccess;
-  const void* fn = us_kernel(a);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kUsLds);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(a.cnt, 0, (size_t)kUsCounters * kUsStride * sizeof(unsigned), st);
-  if (e != hipSuccess) return e;
-  UsArgs arg = a;
-  void* params[] = {&arg};
-  const int G = a.rem ? a.G : kUsG;
-  if (!a.coop) return hipLaunchKernel(fn, dim3(G), dim3(kUsThreads), params, (size_t)kUsLds, st);
-  return hipLaunchCooperativeKernel(fn, dim3(G), dim3(kUsThreads), params, (unsigned)kUsLds, st);
+  return persist::launch(ushape_check(a), us_kernel(a), kUsThreads, kUsLds, a.rem ? a.G : kUsG,
+                         (size_t)kUsCounters * kUsStride * sizeof(unsigned), a, st);
 }
 
 }  // namespace sl

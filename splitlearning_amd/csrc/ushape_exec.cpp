@@ -17,7 +17,7 @@
 #include <tuple>
 #include <vector>
 
-#include "host.h"
+#include "persist_host.h"
 #include "ipc_p2p.h"
 #include "ushape.h"
 
@@ -112,7 +112,7 @@ class UShapeEpoch {
     else {
       if (rem_) {   // placeholders the check requires; the launch's own are set per chunk
         a.lk.sdata[0] = reinterpret_cast<float*>(16);
-        a.lk.rdata[0] = reinterpret_cast<const float*>(16);
+        a.lk.rdata[0] = reinterpret_cast<float*>(16);
       }
       why_ = sl::ushape_check(a);
     }
@@ -185,34 +185,23 @@ class UShapeEpoch {
     labels_ = at::full({S * B_}, -100, lopt);
     labels_.narrow(0, 0, n).copy_(y_.index_select(0, order));
     std::vector<float> tabf(8 * S, 0.f);
-    for (int64_t i = 0; i < S; ++i) {
-      const SlOpt ob = us_opt(bo_, t_b + 1 + i), oa = us_opt(ao_, t_a + 1 + i);
-      tabf[8 * i] = ob.step_size;
-      tabf[8 * i + 1] = ob.inv_bc2_sqrt;
-      tabf[8 * i + 2] = oa.step_size;
-      tabf[8 * i + 3] = oa.inv_bc2_sqrt;
-      tabf[8 * i + 4] = (float)(1.0 / (double)std::min<int64_t>(B_, n - i * B_));
-      tabf[8 * i + 5] = (float)std::min<int64_t>(B_, n - i * B_);
-    }
-    tabf_ = at::from_blob(tabf.data(), {8 * S}, at::TensorOptions().dtype(at::kFloat)).to(dev);
+    sl::host::fill_adam(tabf, 8, 0, t_b, [&](int64_t step) { return us_opt(bo_, step); });
+    sl::host::fill_adam(tabf, 8, 2, t_a, [&](int64_t step) { return us_opt(ao_, step); });
+    sl::host::fill_rows(tabf, 8, 4, 5, [&](int64_t i) { return std::min<int64_t>(B_, n - i * B_); });
+    tabf_ = sl::host::upload(tabf, dev);
     const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
-    TORCH_CHECK(hipMemsetAsync(a_.err, 0, sizeof(int), st) == hipSuccess, "U-shape error word");
-    const int64_t cs = std::min<int64_t>(S, max_steps_);
-    for (int64_t s0 = 0; s0 < S; s0 += cs) {
-      if (s0 > 0 && err_.item<int>() != 0) break;   // a failed chunk stops the epoch
-      const int64_t ns = std::min(cs, S - s0);
+    const int e = sl::host::run_chunks("U-shape", a_.err, err_, st, S, max_steps_, fault_step_,
+                                          [&](int64_t s0, int64_t ns, int fault) {
       sl::UsArgs a = a_;
       a.S = (int)ns;
       a.rows = rows_.data_ptr<int64_t>() + s0 * B_;
       a.Y = labels_.data_ptr<int64_t>() + s0 * B_;
       a.loss = loss_rows.data_ptr<float>() + s0 * B_;
       a.tabf = tabf_.data_ptr<float>() + 8 * s0;
-      a.fault_step = fault_step_ >= s0 && fault_step_ < s0 + ns ? (int)(fault_step_ - s0) : -1;
+      a.fault_step = fault;
       const hipError_t le = sl::ushape_epoch_launch(a, st);
       TORCH_CHECK(le == hipSuccess, "U-shape epoch launch: ", hipGetErrorString(le));
-    }
-    fault_step_ = -1;
-    const int e = err_.item<int>();
+    });
     TORCH_CHECK(e == 0, "U-shape split epoch: an in-launch wait gave up (error word ", e, ")");
     return py::make_tuple(t_a + S, t_b + S);
   }
@@ -229,22 +218,14 @@ class UShapeEpoch {
     const at::Device dev = f1_.W.device();
     auto rows_at = [&](int64_t i) { return std::min<int64_t>(B_, n - i * B_); };
     std::vector<float> tabf(8 * S, 0.f);
-    for (int64_t i = 0; i < S; ++i) {
-      const SlOpt ob = us_opt(bo_, t_b + 1 + i);
-      tabf[8 * i] = ob.step_size;
-      tabf[8 * i + 1] = ob.inv_bc2_sqrt;
-      tabf[8 * i + 4] = (float)(1.0 / (double)rows_at(i));
-      tabf[8 * i + 5] = (float)rows_at(i);
-    }
-    tabf_ = at::from_blob(tabf.data(), {8 * S}, at::TensorOptions().dtype(at::kFloat)).to(dev);
+    sl::host::fill_adam(tabf, 8, 0, t_b, [&](int64_t step) { return us_opt(bo_, step); });
+    sl::host::fill_rows(tabf, 8, 4, 5, rows_at);
+    tabf_ = sl::host::upload(tabf, dev);
     const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
-    TORCH_CHECK(hipMemsetAsync(a_.err, 0, sizeof(int), st) == hipSuccess, "U-shape error word");
-    const int64_t cs = std::min<int64_t>(S, max_steps_);
     const int64_t N2 = a_.N2, cut = (int64_t)sl::kUsCh * sl::kUsP;
     log_.clear();
-    for (int64_t s0 = 0; s0 < S; s0 += cs) {
-      if (s0 > 0 && err_.item<int>() != 0) break;
-      const int64_t ns = std::min(cs, S - s0);
+    const int e = sl::host::run_chunks("U-shape", a_.err, err_, st, S, max_steps_, fault_step_,
+                                          [&](int64_t s0, int64_t ns, int fault) {
       std::vector<int64_t> sends, recvs;
       for (int64_t i = s0; i < s0 + ns; ++i) {
         const int64_t M = rows_at(i);
@@ -260,26 +241,12 @@ class UShapeEpoch {
       const sl::P2PRun r = chan_->run(peer_, st, sends, recvs);
       sl::UsArgs a = a_;
       a.S = (int)ns;
-      for (int p = 0; p < 2; ++p) {
-        a.lk.sdata[p] = r.sdata[p];
-        a.lk.sflag[p] = r.sflag[p];
-        a.lk.sack[p] = r.sack[p];
-        a.lk.rdata[p] = r.rdata[p];
-        a.lk.rflag[p] = r.rflag[p];
-        a.lk.rack[p] = r.rack[p];
-        a.lk.sprev[p] = r.sprev[p];
-      }
-      a.lk.sgen0 = r.sgen0;
-      a.lk.rgen0 = r.rgen0;
-      a.lk.err = r.err;
-      a.lk.herr = r.herr;
+      a.lk = r;
       a.tabf = tabf_.data_ptr<float>() + 8 * s0;
-      a.fault_step = fault_step_ >= s0 && fault_step_ < s0 + ns ? (int)(fault_step_ - s0) : -1;
+      a.fault_step = fault;
       const hipError_t le = sl::ushape_epoch_launch(a, st);
       TORCH_CHECK(le == hipSuccess, "U-shape epoch launch: ", hipGetErrorString(le));
-    }
-    fault_step_ = -1;
-    const int e = err_.item<int>();
+    });
     TORCH_CHECK(e == 0, "U-shape remote split epoch: an in-launch wait gave up (error word ", e, ")");
     return t_b + S;
   }

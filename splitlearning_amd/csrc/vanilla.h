@@ -6,6 +6,7 @@
 // weights, and a forward pass of the next batch over the updated ones.
 #pragma once
 #include "common.h"
+#include "ipc_p2p.h"
 #include "resident.h"
 
 namespace sl {
@@ -30,24 +31,6 @@ constexpr int kVaSeams = 5;         // F: fc2 partials, L: logit partials, D: dl
 // block), CW[32] (conv gradient partials per channel), CX[32] (next-batch activations per channel)
 constexpr int kVaMaxS = 6000;      // steps per launch (the activation slots' 32-bit offsets)
 constexpr int kVaCounters = kVaSeams * 8 + kVaMaxNC + kVaMaxRB + kVaMaxCB + 32 + 32;
-
-// A REMOTE Alice (VaArgs::rem): her conv front runs in her own process (csrc/split.cpp
-// run_alice, unchanged) and the launch speaks the peer-mapped channel's protocol
-// (csrc/ipc_p2p.h) itself: per step i it receives her activation message of step i (generation
-// rgen0 + 1 + i) and sends her the cut gradient of step i (generation sgen0 + 1 + i), each on
-// the parity slot of its generation -- the same messages, sizes and order as run_bob.
-struct VaLink {
-  float* sdata[2];          // her slot data[bob][par]: the cut gradients land there
-  uint32_t* sflag[2];       // her flag words [bob][par][chunk]
-  const uint32_t* sack[2];  // own ack words [alice][par][chunk] (she acks a cut gradient read)
-  const float* rdata[2];    // own slot data[alice][par]: her activation messages
-  const uint32_t* rflag[2]; // own flag words [alice][par][chunk]
-  uint32_t* rack[2];        // her ack words [bob][par][chunk] (acks of her activations)
-  uint32_t sgen0, rgen0;    // the pair's generations before the launch's first message
-  int sprev[2];             // chunk counts of the messages sent two generations before sends 0, 1
-  int* err;                 // the channel's error word (uncached) and its host-pinned mirror
-  int* herr;
-};
 
 struct VaArgs {
   ResLayer L1, L2, L3;    // Bob's tail (v unused: SGD-momentum)
@@ -97,12 +80,19 @@ struct VaArgs {
   int fault_step;         // tests: this step's first wait is never met; -1 off
   int64_t* tall;          // optional [tall_n][G][16] phase stamps (wall clock) of every workgroup
   int tall_step, tall_n;  // for steps tall_step .. tall_step + tall_n - 1
+  // A REMOTE Alice (VaArgs::rem): her conv front runs in her own process (csrc/split.cpp
+  // run_alice, unchanged) and the launch speaks the peer-mapped channel's protocol
+  // (csrc/ipc_p2p.h) itself: per step i it receives her activation message of step i (generation
+  // rgen0 + 1 + i) and sends her the cut gradient of step i (generation sgen0 + 1 + i), each on
+  // the parity slot of its generation -- the same messages, sizes and order as run_bob.
+  // lk is the channel's own P2PRun (csrc/ipc_p2p.h); the kernel only reads through sack / rdata /
+  // rflag, and bounds its channel waits by `timeout` above, not by lk.timeout.
   // remote Alice: the kernel's <true> instantiation; no conv jobs, so G may be any multiple of
   // 8 up to 256 that the fc2 tiling allows (a one-GPU test leaves CUs to the Alice's kernels).
   // Yrem: the launch-local [S * M] labels the kernel fills from the messages (Y unused).
   int rem;
   int64_t* Yrem;
-  VaLink lk;
+  P2PRun lk;
 };
 
 hipError_t vanilla_epoch_launch(const VaArgs& a, hipStream_t st);

@@ -62,6 +62,7 @@
 #include "vanilla.h"
 #include "ipc_ar.h"
 #include "persist.h"
+#include "persist_launch.h"
 
 #include <string>
 
@@ -78,78 +79,6 @@ __device__ __forceinline__ int va_R(int rb) { return kVaSeams * 8 + kVaMaxNC + r
 __device__ __forceinline__ int va_XD(int cb) { return kVaSeams * 8 + kVaMaxNC + kVaMaxRB + cb; }
 __device__ __forceinline__ int va_CW(int c) { return kVaSeams * 8 + kVaMaxNC + kVaMaxRB + kVaMaxCB + c; }
 __device__ __forceinline__ int va_CX(int c) { return kVaSeams * 8 + kVaMaxNC + kVaMaxRB + kVaMaxCB + 32 + c; }
-
-__device__ __forceinline__ bool va_spin(const VaArgs& a, const unsigned* p, unsigned tgt) {
-  if (poll(p) >= tgt) return true;
-  const uint64_t t0 = wall_clock64();
-  while (poll(p) < tgt) {
-    if (failed(a.err)) return false;
-    __builtin_amdgcn_s_sleep(1);
-    if ((int64_t)(wall_clock64() - t0) > a.timeout) {
-      __hip_atomic_fetch_or(a.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-  }
-  return true;
-}
-
-__device__ __forceinline__ void va_arrive(const VaArgs& a, int idx) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(va_cnt(a, idx), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool va_seam_wait(const VaArgs& a, int seam, unsigned mult, int* s_ok, const int* s_sn) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    bool ok = true;
-    if (lane < 8) {
-      const unsigned tg = mult * (unsigned)s_sn[seam * 8 + lane];
-      if (tg > 0) ok = va_spin(a, va_cnt(a, va_seam(seam, lane)), tg);
-    }
-    ok = __all(ok);
-    if (lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  asm volatile("" ::: "memory");   // no load of the handed-off bytes is hoisted above the wait
-  return *s_ok != 0;
-}
-
-// wave 0's lanes [0, n) wait for counters idx0 + lane to reach tgt(lane); uniform result
-template <typename F>
-__device__ __forceinline__ bool va_wait_many(const VaArgs& a, int n, int* s_ok, F tgt_of) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    bool ok = true;
-    if (lane < n) {
-      int idx;
-      const unsigned tg = tgt_of(lane, idx);
-      if (tg > 0) ok = va_spin(a, va_cnt(a, idx), tg);
-    }
-    ok = __all(ok);
-    if (lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  asm volatile("" ::: "memory");   // no load of the handed-off bytes is hoisted above the wait
-  return *s_ok != 0;
-}
-
-// one lane: bounded wait until the channel flag / ack word *f reaches generation `want`
-// (remote Alice); a timeout raises the launch's error word and the channel's
-__device__ __forceinline__ bool va_pwait(const VaArgs& a, const uint32_t* f, uint32_t want) {
-  if ((int32_t)(ipc_poll_flag(f) - want) >= 0) return true;
-  const uint64_t t0 = wall_clock64();
-  while ((int32_t)(ipc_poll_flag(f) - want) < 0) {
-    if (failed(a.err)) return false;
-    __builtin_amdgcn_s_sleep(1);
-    if ((int64_t)(wall_clock64() - t0) > a.timeout) {
-      __hip_atomic_fetch_or(a.err, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ipc_fail(a.lk.err, a.lk.herr);
-      return false;
-    }
-  }
-  return true;
-}
 
 constexpr int kSt = 16;   // fc1 W / buf loads and stores: sc1 (write-through stores, L1-bypassing loads)
 constexpr int kVaFwdRing = 6;   // forward-pass register ring depth (tiles; kVaFwdRing - 1 in flight)
@@ -462,7 +391,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
   };
   // every update run of step i has stored and drained its tiles (the W the forward pass reads)
   auto wait_all_xd = [&](int i) {
-    return va_wait_many(a, ncb, s_ok, [&](int l, int& idx) {
+    return wait_lanes(a.err, a.timeout, a.cnt, kVaStride, ncb, s_ok, [&](int l, int& idx) {
       idx = va_XD(l);
       return (unsigned)(i + 1) * (unsigned)a.tab[a.oU + l];
     });
@@ -606,7 +535,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) dacc[c] = zv;
-    va_arrive(a, va_XD(cb));
+    arrive(a.cnt, kVaStride, va_XD(cb));
   };
   auto upd_pass = [&](int step, float ss, float ib) {
     if (unt <= 0) return;
@@ -691,7 +620,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
       if (lane < na) c = ca0 + lane;
       else if (lane >= 32 && lane - 32 < nl) c = cl0 + lane - 32;
       bool ok = true;
-      if (c >= 0) ok = va_pwait(a, a.lk.rflag[par] + c, rg);
+      if (c >= 0) ok = chan_wait(a.err, a.timeout, a.lk, a.lk.rflag[par] + c, rg);
       ok = __all(ok);
       ipc_acquire();
       if (lane == 0) *s_ok = ok ? 1 : 0;
@@ -733,7 +662,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
     const int len = rows_of(i) * K1;
     const int nch = (len + kIpcChunk - 1) / kIpcChunk;
     if (w >= nch) return true;
-    if (!va_wait_many(a, ncb, s_ok, [&](int l, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kVaStride, ncb, s_ok, [&](int l, int& idx) {
           idx = va_XD(l);
           return (unsigned)(i + 1) * (unsigned)a.tab[a.oU + l];
         }))
@@ -745,7 +674,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
     for (int c = w; c < nch; c += G) {
       if (threadIdx.x == 0) {
         // chunks beyond the message two generations back wait on its chunk 0 (ipc_p2p.hip)
-        const bool ok = prev == 0 || va_pwait(a, a.lk.sack[par] + (c < prev ? c : 0), sg - 2u);
+        const bool ok = prev == 0 || chan_wait(a.err, a.timeout, a.lk, a.lk.sack[par] + (c < prev ? c : 0), sg - 2u);
         ipc_acquire();
         *s_ok = ok ? 1 : 0;
       }
@@ -775,15 +704,15 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
   // seam X: every activation of the next batch published (arrive, `between`, then wait);
   // REM: every workgroup's share of her message (8 shards), co-located: per channel (kVaSeamXByChannel)
   auto seam_x = [&](unsigned mult, auto between) -> bool {
-    if (!REM && kVaSeamXByChannel) va_arrive(a, va_CX(cc));
-    else va_arrive(a, va_seam(4, w & 7));
+    if (!REM && kVaSeamXByChannel) arrive(a.cnt, kVaStride, va_CX(cc));
+    else arrive(a.cnt, kVaStride, va_seam(4, w & 7));
     if (!between()) return false;
     if (!REM && kVaSeamXByChannel)
-      return va_wait_many(a, 32, s_ok, [&](int l, int& idx) {
+      return wait_lanes(a.err, a.timeout, a.cnt, kVaStride, 32, s_ok, [&](int l, int& idx) {
         idx = va_CX(l);
         return mult * 8u;
       });
-    return va_seam_wait(a, 4, mult, s_ok, s_sn);
+    return seam_wait(a.err, a.timeout, a.cnt, kVaStride, 4, mult, s_sn, s_ok);
   };
 
   // ---- prologue: Alice's forward of batch 0 (REM: her message of it), then the forward pass
@@ -819,7 +748,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
       if (rlo + lane <= rhi) {
         const int rb = rlo + lane;
         const unsigned tg = i == a.fault_step ? 0xffffffffu : (unsigned)(i + 1) * (unsigned)s_fns[lane];
-        ok = va_spin(a, va_cnt(a, va_R(rb)), tg);
+        ok = spin(a.err, a.timeout, va_cnt(a, va_R(rb)), tg);
       }
       ok = __all(ok);
       if (lane == 0) *s_ok = ok ? 1 : 0;
@@ -874,12 +803,12 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
         if (n < WR) hst4(rHB, bFP + (((par * NC + tb) * N2 + r0 + n) * 16 + 4 * lq) * 4, acc);
       }
     }
-    va_arrive(a, va_seam(0, w & 7));
+    arrive(a.cnt, kVaStride, va_seam(0, w & 7));
 
     VA_MARK(2);
     // ================= H: the head rows' fc2 sums, h2, logit partials
     if (head) {
-      if (!va_seam_wait(a, 0, (unsigned)(i + 1), s_ok, s_sn)) break;
+      if (!seam_wait(a.err, a.timeout, a.cnt, kVaStride, 0, (unsigned)(i + 1), s_sn, s_ok)) break;
       {
         VA_IDX();
         const int cq = tid >> 4, ii = (tid >> 2) & 3, mg = tid & 3;
@@ -909,12 +838,12 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
           }
         }
       }
-      va_arrive(a, va_seam(1, w & 7));
+      arrive(a.cnt, kVaStride, va_seam(1, w & 7));
     }
 
     // ================= S: row m's logits, softmax-CE, dlogits (workgroups m < M)
     if (w < M) {
-      if (!va_seam_wait(a, 1, (unsigned)(i + 1), s_ok, s_sn)) break;
+      if (!seam_wait(a.err, a.timeout, a.cnt, kVaStride, 1, (unsigned)(i + 1), s_sn, s_ok)) break;
       const int m = w;
       const int nc4 = C4 >> 2;
       constexpr int NG = kVaThreads / 32;
@@ -985,12 +914,12 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
         if (act) hst4(rHB, bDL + ((par * 16 + m) * C4 + 4 * c4) * 4, d);
         if (tid == 0) a.loss[(int64_t)i * M + m] = ign ? 0.f : mx + logf(se) - zl;
       }
-      va_arrive(a, va_seam(2, w & 7));
+      arrive(a.cnt, kVaStride, va_seam(2, w & 7));
     }
 
     // ================= H2: dz2 of the head rows; b3 / W3 / b2 steps
     if (head) {
-      if (!va_seam_wait(a, 2, (unsigned)(i + 1), s_ok, s_sn)) break;
+      if (!seam_wait(a.err, a.timeout, a.cnt, kVaStride, 2, (unsigned)(i + 1), s_sn, s_ok)) break;
       {
         VA_IDX();
         for (int e = tid; e < 16 * (MC / 4); e += kVaThreads) {
@@ -1018,7 +947,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
       __syncthreads();
       if (threadIdx.x < 16 && (int)threadIdx.x < M)
         hst4(rHB, bDZ + ((par * 16 + threadIdx.x) * N2 + 4 * w) * 4, *reinterpret_cast<const f32x4*>(sdzh + threadIdx.x * 4));
-      va_arrive(a, va_seam(3, w & 7));
+      arrive(a.cnt, kVaStride, va_seam(3, w & 7));
       {
         VA_IDX();
         float dummy = 0.f;
@@ -1048,7 +977,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
 
     VA_MARK(3);
     // ================= B: the tile's dz1 partial, then W2's step
-    if (!va_seam_wait(a, 3, (unsigned)(i + 1), s_ok, s_sn)) break;
+    if (!seam_wait(a.err, a.timeout, a.cnt, kVaStride, 3, (unsigned)(i + 1), s_sn, s_ok)) break;
     VA_MARK(3);
     {
       VA_IDX();
@@ -1089,7 +1018,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
         }
       }
     }
-    va_arrive(a, va_P(tb));
+    arrive(a.cnt, kVaStride, va_P(tb));
     VA_MARK(4);
     // the first update tile's state in flight under W2's update and the dz1 wait
     if (unt > 0) load_u(u_begin, sp[0], sm[0]);
@@ -1120,7 +1049,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
     {
       // every fc2 column block's dz1 partials (the update run spans ~27 row blocks, possibly
       // wrapping to the next column block's top)
-      if (!va_wait_many(a, NC, s_ok, [&](int l, int& idx) {
+      if (!wait_lanes(a.err, a.timeout, a.cnt, kVaStride, NC, s_ok, [&](int l, int& idx) {
             idx = va_P(l);
             return (unsigned)(i + 1) * kVaNR;
           }))
@@ -1183,13 +1112,13 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
       VA_MARK(9);
       if (more) {
         if (!recv_act(i + 1)) break;
-        va_arrive(a, va_seam(4, w & 7));
+        arrive(a.cnt, kVaStride, va_seam(4, w & 7));
         VA_MARK(12);
         if constexpr (kVaFwdPre > 0) {
           if (!wait_all_xd(i)) break;
           fwd_prefetch();
         }
-        if (!va_seam_wait(a, 4, (unsigned)(i + 2), s_ok, s_sn)) break;
+        if (!seam_wait(a.err, a.timeout, a.cnt, kVaStride, 4, (unsigned)(i + 2), s_sn, s_ok)) break;
         VA_MARK(13);
         ack_act(i + 1);
         fwd_pass(i + 1);
@@ -1202,7 +1131,7 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
     // ================= C: Alice's backward + step (conv job), her forward of batch i + 1
     {
       const int k0 = cc * 169, cblo = k0 >> 8, cbhi = (k0 + 168) >> 8;
-      if (!va_wait_many(a, cbhi - cblo + 1, s_ok, [&](int l, int& idx) {
+      if (!wait_lanes(a.err, a.timeout, a.cnt, kVaStride, cbhi - cblo + 1, s_ok, [&](int l, int& idx) {
             idx = va_XD(cblo + l);
             return (unsigned)(i + 1) * (unsigned)a.tab[a.oU + cblo + l];
           }))
@@ -1252,9 +1181,9 @@ __global__ void __launch_bounds__(kVaThreads) vanilla_epoch_kernel(VaArgs a) {
       for (int ww = 1; ww < 8; ++ww) g += scred[ww * 16 + j];
       hst1(rHB, bCW + (((par * 32 + cc) * 8 + cg) * 16 + j) * 4, g);
     }
-    va_arrive(a, va_CW(cc));
+    arrive(a.cnt, kVaStride, va_CW(cc));
     VA_MARK(10);
-    if (!va_wait_many(a, 1, s_ok, [&](int, int& idx) {
+    if (!wait_lanes(a.err, a.timeout, a.cnt, kVaStride, 1, s_ok, [&](int, int& idx) {
           idx = va_CW(cc);
           return (unsigned)(i + 1) * 8u;
         }))
@@ -1374,39 +1303,19 @@ std::string vanilla_check(const VaArgs& a) {
   return "";
 }
 
+// the instantiation a launch uses: a co-located or a remote Alice
+static const void* vanilla_fn(const VaArgs& a) {
+  return a.rem ? reinterpret_cast<const void*>(&vanilla_epoch_kernel<true>)
+               : reinterpret_cast<const void*>(&vanilla_epoch_kernel<false>);
+}
+
 bool vanilla_fits(const VaArgs& a, int device, std::string* why) {
-  std::string s = vanilla_check(a);
-  if (s.empty()) {
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, device) != hipSuccess) {
-      s = "device properties";
-    } else {
-      const void* fn = a.rem ? reinterpret_cast<const void*>(&vanilla_epoch_kernel<true>)
-                             : reinterpret_cast<const void*>(&vanilla_epoch_kernel<false>);
-      int nb = 0;
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kVaLds);
-      if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kVaThreads, kVaLds);
-      if (e != hipSuccess || nb < 1) s = "occupancy";
-      else if ((int64_t)nb * pr.multiProcessorCount < a.G) s = "workgroups not co-resident";
-    }
-  }
-  if (why) *why = s;
-  return s.empty();
+  return persist::fits(vanilla_check(a), vanilla_fn(a), kVaThreads, kVaLds, a.G, device, why);
 }
 
 hipError_t vanilla_epoch_launch(const VaArgs& a, hipStream_t st) {
-  if (!vanilla_check(a).empty()) return hipErrorInvalidValue;
-  if (a.S <= 0) return hipSuccess;
-  const void* fn = a.rem ? reinterpret_cast<const void*>(&vanilla_epoch_kernel<true>)
-                         : reinterpret_cast<const void*>(&vanilla_epoch_kernel<false>);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kVaLds);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(a.cnt, 0, (size_t)kVaCounters * kVaStride * sizeof(unsigned), st);
-  if (e != hipSuccess) return e;
-  VaArgs arg = a;
-  void* params[] = {&arg};
-  if (!a.coop) return hipLaunchKernel(fn, dim3(a.G), dim3(kVaThreads), params, (size_t)kVaLds, st);
-  return hipLaunchCooperativeKernel(fn, dim3(a.G), dim3(kVaThreads), params, (unsigned)kVaLds, st);
+  return persist::launch(vanilla_check(a), vanilla_fn(a), kVaThreads, kVaLds, a.G,
+                         (size_t)kVaCounters * kVaStride * sizeof(unsigned), a, st);
 }
 
 }  // namespace sl

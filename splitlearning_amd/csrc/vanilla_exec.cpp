@@ -19,7 +19,7 @@
 #include <tuple>
 #include <vector>
 
-#include "host.h"
+#include "persist_host.h"
 #include "ipc_p2p.h"
 #include "vanilla.h"
 
@@ -125,7 +125,7 @@ class VanillaEpoch {
       // placeholders the check requires; the launch's own are set per chunk
       a.Yrem = reinterpret_cast<int64_t*>(16);
       a.lk.sdata[0] = reinterpret_cast<float*>(16);
-      a.lk.rdata[0] = reinterpret_cast<const float*>(16);
+      a.lk.rdata[0] = reinterpret_cast<float*>(16);
       if (chan_->cap() < act_words(B_)) why_ = "the channel is too small for a batch";
     }
     if (why_.empty()) why_ = sl::vanilla_check(a);
@@ -233,7 +233,7 @@ class VanillaEpoch {
   // (op, peer, bytes) of every message the last run_remote issued, in issue order (run_bob's)
   std::vector<std::tuple<std::string, int, int64_t>> messages() const { return log_; }
 
-  void set_fault_step(int64_t s) { fault_step_ = (int)s; }
+  void set_fault_step(int64_t s) { fault_step_ = s; }
   bool remote() const { return rem_; }
   int workgroups() const { return a_.G; }
   void set_max_steps(int64_t s) { max_steps_ = std::max<int64_t>(1, std::min<int64_t>(s, sl::kVaMaxS)); }
@@ -251,33 +251,19 @@ class VanillaEpoch {
              const c10::optional<at::Tensor>& trace_all, int64_t trace_step, const at::Device& dev) {
     TORCH_CHECK(loss_rows.is_cuda() && loss_rows.scalar_type() == at::kFloat && loss_rows.numel() >= S * B_,
                 "loss_rows f32 [>= S * B]");
-    std::vector<float> tabf(4 * S, 0.f);
-    std::vector<int32_t> seeds(4 * S);
     auto rows_at = [&](int64_t i) { return (int)std::min<int64_t>(B_, n - i * B_); };
-    for (int64_t i = 0; i < S; ++i) {
-      const int64_t rows = rows_at(i);
-      tabf[4 * i] = (float)rows;
-      tabf[4 * i + 2] = (float)(1.0 / (double)rows);
-      const uint64_t s0 = sl::step_seed((uint64_t)seed_base, 0, (uint64_t)(fwd_count + 1 + i));
-      const uint64_t s1 = sl::step_seed((uint64_t)seed_base, 1, (uint64_t)(fwd_count + 1 + i));
-      seeds[4 * i] = (int32_t)(uint32_t)(s0 & 0xffffffffull);
-      seeds[4 * i + 1] = (int32_t)(uint32_t)(s0 >> 32);
-      seeds[4 * i + 2] = (int32_t)(uint32_t)(s1 & 0xffffffffull);
-      seeds[4 * i + 3] = (int32_t)(uint32_t)(s1 >> 32);
-    }
-    tabf_ = at::from_blob(tabf.data(), {4 * S}, at::TensorOptions().dtype(at::kFloat)).to(dev);
-    seeds_ = at::from_blob(seeds.data(), {4 * S}, at::TensorOptions().dtype(at::kInt)).to(dev);
+    std::vector<float> tabf(4 * S, 0.f);
+    sl::host::fill_rows(tabf, 4, 2, 0, rows_at);
+    tabf_ = sl::host::upload(tabf, dev);
+    seeds_ = sl::host::step_seeds(S, seed_base, fwd_count, dev);
     const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
-    TORCH_CHECK(hipMemsetAsync(a_.err, 0, sizeof(int), st) == hipSuccess, "vanilla error word");
     // launches of at most kVaMaxS steps (one launch of S steps is bitwise S one-step launches)
     const int64_t cs = std::min<int64_t>(S, max_steps_);
     xr_ = at::empty({cs * 16 * a_.K1}, at::TensorOptions().dtype(at::kFloat).device(dev));
     if (rem_) yrem_ = at::empty({cs * B_}, at::TensorOptions().dtype(at::kLong).device(dev));
     log_.clear();
-    for (int64_t s0 = 0; s0 < S; s0 += cs) {
-      // a chunk whose wait gave up stops the epoch here (host check between chunks, as HybridEpoch)
-      if (s0 > 0 && err_.item<int>() != 0) break;
-      const int64_t ns = std::min(cs, S - s0);
+    const int e = sl::host::run_chunks("vanilla", a_.err, err_, st, S, max_steps_, fault_step_,
+                                          [&](int64_t s0, int64_t ns, int fault) {
       sl::VaArgs a = a_;
       a.S = (int)ns;
       a.Xr = xr_.data_ptr<float>();
@@ -292,20 +278,7 @@ class VanillaEpoch {
           log_.emplace_back("recv", peer_, recvs.back() * 4);
           log_.emplace_back("send", peer_, sends.back() * 4);
         }
-        const sl::P2PRun r = chan_->run(peer_, st, sends, recvs);
-        for (int p = 0; p < 2; ++p) {
-          a.lk.sdata[p] = r.sdata[p];
-          a.lk.sflag[p] = r.sflag[p];
-          a.lk.sack[p] = r.sack[p];
-          a.lk.rdata[p] = r.rdata[p];
-          a.lk.rflag[p] = r.rflag[p];
-          a.lk.rack[p] = r.rack[p];
-          a.lk.sprev[p] = r.sprev[p];
-        }
-        a.lk.sgen0 = r.sgen0;
-        a.lk.rgen0 = r.rgen0;
-        a.lk.err = r.err;
-        a.lk.herr = r.herr;
+        a.lk = chan_->run(peer_, st, sends, recvs);
         a.Yrem = yrem_.data_ptr<int64_t>();
         a.rows = nullptr;
         a.Y = nullptr;
@@ -321,12 +294,10 @@ class VanillaEpoch {
         a.tall_n = (int)(trace_all->numel() / (16LL * a_.G));
         a.tall_step = (int)(trace_step - s0);
       }
-      a.fault_step = fault_step_ >= s0 && fault_step_ < s0 + ns ? (int)(fault_step_ - s0) : -1;
+      a.fault_step = fault;
       const hipError_t le = sl::vanilla_epoch_launch(a, st);
       TORCH_CHECK(le == hipSuccess, "vanilla epoch launch: ", hipGetErrorString(le));
-    }
-    fault_step_ = -1;
-    const int e = err_.item<int>();
+    });
     TORCH_CHECK(e == 0, "vanilla split epoch: an in-launch wait gave up (error word ", e, ")");
   }
 
@@ -433,7 +404,8 @@ class VanillaEpoch {
 
   at::Tensor W_[3], b_[3], s0_[3], sb0_[3];
   at::Tensor cw_, cb_, cmw_, cmb_, x_, y_;
-  int B_ = 16, dev_ = 0, fault_step_ = -1;
+  int B_ = 16, dev_ = 0;
+  int64_t fault_step_ = -1;
   int64_t max_steps_ = sl::kVaMaxS;
   double timeout_s_ = 30.0;
   sl::VaArgs a_{};

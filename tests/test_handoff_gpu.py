@@ -1,7 +1,10 @@
-"""The persistent kernels' in-launch publication primitive (csrc/persist.h, used by
-csrc/resident.hip, hybrid.hip and vanilla.hip), stress-tested word by word on the GPU
-(csrc/handoff.hip): producers on every XCD rewrite a payload IN PLACE every round (as the
-vanilla epoch's fc1 tiles are rewritten between its update and forward passes), consumers
+"""The persistent kernels' in-launch publication primitive (csrc/persist.h), stress-tested word
+by word on the GPU (csrc/handoff.hip).  The four one-launch epochs (csrc/resident.hip,
+hybrid.hip, vanilla.hip, ushape.hip) hand off in this form and all wait through persist.h's
+spin; the stress kernel runs the primitive the kernels run: the very arrive / seam_wait that
+resident.hip and vanilla.hip call (hybrid.hip's seam wait and ushape.hip's arrive are the same
+code kept in those files, docs/PERF.md says why).  Producers on every XCD rewrite a payload IN
+PLACE every round (as the vanilla epoch's fc1 tiles are rewritten between its update and forward passes), consumers
 re-read the same addresses every round (L1 / L2 warm with the previous round's value), random
 per-round delays and a bandwidth stream on a random half of the workgroups make the load
 uneven (MI355X_MICROARCH.md: "test every hand-off under UNEVEN load, consumer L1-warm,
