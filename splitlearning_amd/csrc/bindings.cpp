@@ -18,6 +18,7 @@
 #include "fused.h"
 #include "handoff.h"
 #include "host.h"
+#include "optim.h"
 
 namespace sl {
 hipError_t conv_fwd(const void* x, bool x_u8, const int64_t* idx, int64_t row0, int B, const float* w,
@@ -550,6 +551,94 @@ void opt_flat(at::Tensor& p, const at::Tensor& g, at::Tensor& s0, const OptT& s1
         "opt_flat");
 }
 
+// ---------------------------------------------------------------- multi-tensor optimizer
+// optim.hip: lists of flat fp32 tensors, cut into launches of at most kMultiOptMax entries.
+void need_flat(const at::Tensor& t, const at::Tensor& like, const char* name) {
+  need_f32(t, name);
+  TORCH_CHECK(t.device() == like.device(), name, " must be on the parameters' device");
+  TORCH_CHECK(t.is_contiguous() && t.numel() == like.numel(), name, " must be contiguous with the parameter's numel");
+}
+
+// Appends `e` (n > 0 elements) to the table, launching the table first when it is full.
+template <class Launch>
+void table_add(sl::MultiOptTable& tab, sl::MultiOptTensor e, Launch&& launch) {
+  const int64_t nc = (e.n + sl::kMultiOptChunk - 1) / sl::kMultiOptChunk;
+  TORCH_CHECK(nc <= INT32_MAX, "tensor too large for one launch");
+  if (tab.k == sl::kMultiOptMax || (int64_t)tab.chunks + nc > INT32_MAX) {
+    launch(tab);
+    tab.k = tab.chunks = 0;
+  }
+  e.chunk0 = tab.chunks;
+  tab.t[tab.k++] = e;
+  tab.chunks += (int)nc;
+}
+
+// One optimizer step over params[i] with grads[i] and state s0s[i] (, s1s[i] for Adam); s0s
+// may be empty for SGD without momentum.  gscale: a device float every gradient is multiplied
+// by first (clipping), or None.  Zero-element tensors are skipped.
+void multi_opt(const std::vector<at::Tensor>& ps, const std::vector<at::Tensor>& gs,
+               const std::vector<at::Tensor>& s0s, const std::vector<at::Tensor>& s1s, OPT_ARGS, const OptT& gscale) {
+  TORCH_CHECK(kind == 1 || kind == 2, "multi_opt: kind 1 (SGD) or 2 (Adam)");
+  const size_t k = ps.size();
+  const bool has_s0 = !s0s.empty();
+  TORCH_CHECK(gs.size() == k, "multi_opt: one gradient per parameter");
+  TORCH_CHECK(s0s.size() == k || (!has_s0 && kind == 1 && momentum == 0.0), "multi_opt: one s0 per parameter");
+  TORCH_CHECK(kind != 2 || s1s.size() == k, "multi_opt: Adam needs one s1 per parameter");
+  if (k == 0) return;
+  const float* gsc = nullptr;
+  if (gscale.has_value() && gscale->defined()) {
+    need_f32(*gscale, "gscale");
+    TORCH_CHECK(gscale->numel() >= 1 && gscale->device() == ps[0].device(), "gscale: a float on the parameters' device");
+    gsc = gscale->data_ptr<float>();
+  }
+  const SlOpt o = OPT_PASS;
+  const hipStream_t st = cur_stream();
+  auto launch = [&](const sl::MultiOptTable& tab) { check(sl::multi_opt(tab, o, gsc, st), "multi_opt"); };
+  sl::MultiOptTable tab{};
+  for (size_t i = 0; i < k; ++i) {
+    need_f32(ps[i], "param");
+    TORCH_CHECK(ps[i].is_contiguous() && ps[i].device() == ps[0].device(), "params: contiguous, on one device");
+    need_flat(gs[i], ps[i], "grad");
+    if (has_s0) need_flat(s0s[i], ps[i], "s0");
+    if (kind == 2) need_flat(s1s[i], ps[i], "s1");
+    if (ps[i].numel() == 0) continue;
+    table_add(tab, sl::MultiOptTensor{ps[i].data_ptr<float>(), gs[i].data_ptr<float>(),
+                                      has_s0 ? s0s[i].data_ptr<float>() : nullptr,
+                                      kind == 2 ? s1s[i].data_ptr<float>() : nullptr, ps[i].numel(), 0},
+              launch);
+  }
+  if (tab.k) launch(tab);
+}
+
+// Global L2 norm of `gs`: out3 = {sum of squares, norm, min(1, max_norm / (norm + 1e-6))},
+// through one partial sum per chunk in `ws`.  Deterministic (no atomics, fixed orders).
+void grad_norm(const std::vector<at::Tensor>& gs, double max_norm, at::Tensor& out3, at::Tensor& ws) {
+  need_f32(out3, "out3");
+  need_f32(ws, "workspace");
+  TORCH_CHECK(out3.is_contiguous() && out3.numel() >= 3 && ws.is_contiguous(), "out3 [3], contiguous workspace");
+  TORCH_CHECK(ws.device() == out3.device(), "workspace on out3's device");
+  int64_t total = 0;
+  for (const auto& g : gs) {
+    need_f32(g, "grad");
+    TORCH_CHECK(g.is_contiguous() && g.device() == out3.device(), "grads: contiguous, on out3's device");
+    total += (g.numel() + sl::kMultiOptChunk - 1) / sl::kMultiOptChunk;
+  }
+  TORCH_CHECK(ws.numel() >= total, "grad_norm workspace: one float per chunk");
+  const hipStream_t st = cur_stream();
+  float* slots = ws.data_ptr<float>();
+  auto launch = [&](const sl::MultiOptTable& tab) {
+    check(sl::grad_sumsq(tab, slots, st), "grad_sumsq");
+    slots += tab.chunks;
+  };
+  sl::MultiOptTable tab{};
+  for (const auto& g : gs) {
+    if (g.numel() == 0) continue;
+    table_add(tab, sl::MultiOptTensor{nullptr, g.data_ptr<float>(), nullptr, nullptr, g.numel(), 0}, launch);
+  }
+  if (tab.k) launch(tab);
+  check(sl::grad_norm_finish(ws.data_ptr<float>(), total, (float)max_norm, out3.data_ptr<float>(), st), "grad_norm_finish");
+}
+
 // ---------------------------------------------------------------- loss / metrics
 void softmax_ce(const at::Tensor& x, const at::Tensor& y, int64_t ignore, double scale, at::Tensor& loss_rows,
                 const OptT& d) {
@@ -740,6 +829,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_nn_dgrad", &gemm_nn_dgrad);
   m.def("linear_wgrad_opt", &linear_wgrad_opt);
   m.def("opt_flat", &opt_flat);
+  m.def("multi_opt", &multi_opt);
+  m.def("grad_norm", &grad_norm);
+  m.attr("multi_opt_chunk") = (int64_t)sl::kMultiOptChunk;
+  m.attr("multi_opt_max") = (int64_t)sl::kMultiOptMax;
   m.def("softmax_ce", &softmax_ce);
   m.def("eval_counters", &eval_counters);
   m.def("relu_mask", &relu_mask);

@@ -2,8 +2,10 @@
 
 The engines (engine/) drive the reference architectures without autograd: they know
 the whole step and fuse it. A user who builds a different split model out of ordinary
-`nn.Module`s and trains it with `loss.backward()` and a `torch.optim` optimizer can use
-these layers instead, and still gets the fused kernels on an MI355X:
+`nn.Module`s and trains it with `loss.backward()` and an optimizer can use these layers
+instead, and still gets the fused kernels on an MI355X; `splitlearning_amd.optim.FusedSGD`
+/ `FusedAdam` are the matching optimizers (one launch per parameter group, optional global
+gradient-norm clipping), and any `torch.optim` optimizer works too:
 
 * `FusedLinear`: Linear + optional ReLU + optional dropout in one forward kernel
   (the skinny split-K MFMA GEMM for batches <= 128, hipBLASLt + fused epilogue above).

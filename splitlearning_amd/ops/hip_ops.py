@@ -317,6 +317,48 @@ def apply_update_(p, g, st, cfg, t):
     C().opt_flat(p.detach(), g, _s0(st), _s1(st), *_opt_args(cfg, t))
 
 
+# ---------------------------------------------------------------- multi-tensor optimizer
+# csrc/optim.h's kMultiOptChunk / kMultiOptMax: elements per workgroup and tensors per launch
+# (checked against the extension on first use; tests size their tensors around them).
+MULTI_OPT_CHUNK = 2048
+MULTI_OPT_MAX = 64
+_MULTI_OPT_CHECKED = False
+
+
+def _multi_opt_C():
+    global _MULTI_OPT_CHECKED
+    c = C()
+    if not _MULTI_OPT_CHECKED:
+        if (c.multi_opt_chunk, c.multi_opt_max) != (MULTI_OPT_CHUNK, MULTI_OPT_MAX):
+            raise RuntimeError("hip_ops.MULTI_OPT_CHUNK / MULTI_OPT_MAX differ from csrc/optim.h")
+        _MULTI_OPT_CHECKED = True
+    return c
+
+
+def multi_update_(ps, gs, sts, cfg, t, gscale=None):
+    """`apply_update_` over lists of tensors in one launch per MULTI_OPT_MAX tensors
+    (csrc/optim.hip), bitwise the per-tensor result.  `gscale`: a one-float device tensor every
+    gradient is multiplied by first (the clip coefficient of `grad_norm`).  An SGD state
+    without momentum may carry no buffer ({"buf": None})."""
+    s0s = [_s0(st) for st in sts]
+    if cfg.kind == "sgd" and not cfg.momentum and all(s is None for s in s0s):
+        s0s = []
+    s1s = [_s1(st) for st in sts] if cfg.kind == "adam" else []
+    _multi_opt_C().multi_opt([p.detach() for p in ps], list(gs), s0s, s1s, *_opt_args(cfg, t), gscale)
+
+
+def grad_norm(gs, max_norm: float):
+    """{sum of squares, L2 norm, min(1, max_norm / (norm + 1e-6))} over all of `gs` as a
+    3-float device tensor (torch.nn.utils.clip_grad_norm_'s rule), deterministic and without
+    a host synchronisation."""
+    gs = list(gs)
+    dev = gs[0].device
+    chunks = sum((g.numel() + MULTI_OPT_CHUNK - 1) // MULTI_OPT_CHUNK for g in gs)
+    out = torch.empty(3, device=dev, dtype=torch.float32)
+    _multi_opt_C().grad_norm(gs, float(max_norm), out, _workspace(dev, chunks, "gnorm"))
+    return out
+
+
 # ---------------------------------------------------------------- fused server step
 def linear_fwd_partial(x, w, max_split: int = 16, key: str = "fc2p"):
     """x @ w.T as un-reduced split-K slabs [S, M, N] (S = 1: the plain product)."""

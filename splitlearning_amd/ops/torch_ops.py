@@ -142,6 +142,22 @@ def apply_update_(p, g, st: dict, cfg, t: int):
         raise ValueError(cfg.kind)
 
 
+def multi_update_(ps, gs, sts, cfg, t: int, gscale=None):
+    """`apply_update_` over lists of tensors; `gscale` (a one-float tensor) multiplies every
+    gradient first."""
+    with torch.no_grad():
+        for p, g, st in zip(ps, gs, sts):
+            apply_update_(p, g if gscale is None else g * gscale, st, cfg, t)
+
+
+def grad_norm(gs, max_norm: float):
+    """{sum of squares, L2 norm, min(1, max_norm / (norm + 1e-6))} over all of `gs`
+    (torch.nn.utils.clip_grad_norm_'s rule) as a 3-float tensor."""
+    norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g) for g in gs]))
+    coef = torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+    return torch.stack([norm * norm, norm, coef])
+
+
 def linear_wgrad_step_(dz, a, w, b, cfg, st_w: dict, st_b: dict, t: int):
     with torch.no_grad():
         dw, db = linear_wgrad(dz, a)
