@@ -19,6 +19,7 @@
 #include "handoff.h"
 #include "host.h"
 #include "optim.h"
+#include "conv2d.h"
 
 namespace sl {
 hipError_t conv_fwd(const void* x, bool x_u8, const int64_t* idx, int64_t row0, int B, const float* w,
@@ -639,6 +640,110 @@ void grad_norm(const std::vector<at::Tensor>& gs, double max_norm, at::Tensor& o
   check(sl::grad_norm_finish(ws.data_ptr<float>(), total, (float)max_norm, out3.data_ptr<float>(), st), "grad_norm_finish");
 }
 
+// ---------------------------------------------------------------- general 3x3 conv (conv2d.hip)
+// x [B, Cin, H, W], w [Cout, Cin, 3, 3], y / dy / am [B, Cout, Hy, Wy]: contiguous, fp32 (am
+// uint8), on the current device, each under 2 GB (the kernels index with 32-bit byte offsets).
+void conv_need(const at::Tensor& t, const at::Tensor& like, const char* name, bool u8 = false) {
+  need_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == (u8 ? at::kByte : at::kFloat), name, u8 ? " must be uint8" : " must be float32");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.device() == like.device() && t.get_device() == c10::hip::current_device(), name,
+              " must be on the current device");
+  TORCH_CHECK(t.numel() * (int64_t)t.element_size() < (int64_t(1) << 31), name, " must be under 2 GB");
+}
+
+sl::Conv2dShape conv_shape(at::IntArrayRef x, at::IntArrayRef w, int64_t pad, bool relu, int64_t pool) {
+  TORCH_CHECK(x.size() == 4 && w.size() == 4, "conv3x3: x [B, Cin, H, W], w [Cout, Cin, 3, 3]");
+  TORCH_CHECK(w[1] == x[1] && w[2] == 3 && w[3] == 3, "conv3x3: w must be [Cout, Cin, 3, 3]");
+  TORCH_CHECK(pad == 0 || pad == 1, "conv3x3: padding 0 or 1");
+  TORCH_CHECK(pool == 0 || pool == 2, "conv3x3: pool 0 (none) or 2");
+  TORCH_CHECK(x[0] >= 1 && x[1] >= 1 && w[0] >= 1 && x[2] >= 3 && x[3] >= 3, "conv3x3: empty or too small input");
+  sl::Conv2dShape s;
+  s.B = (int)x[0], s.Cin = (int)x[1], s.H = (int)x[2], s.W = (int)x[3], s.Cout = (int)w[0];
+  s.pad = (int)pad, s.relu = relu, s.pool = pool == 2;
+  s.Ho = s.H + 2 * s.pad - 2, s.Wo = s.W + 2 * s.pad - 2;
+  s.Hy = s.pool ? s.Ho / 2 : s.Ho, s.Wy = s.pool ? s.Wo / 2 : s.Wo;
+  TORCH_CHECK(s.Hy >= 1 && s.Wy >= 1, "conv3x3: the pooled conv output must be at least 2x2");
+  // the un-stored conv output is indexed with 32-bit integers too
+  TORCH_CHECK((int64_t)s.B * s.Cout * s.Ho * s.Wo < (int64_t(1) << 29), "conv3x3: conv output too large");
+  return s;
+}
+
+void conv_check_y(const at::Tensor& t, const sl::Conv2dShape& s, const char* name) {
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == s.B && t.size(1) == s.Cout && t.size(2) == s.Hy && t.size(3) == s.Wy, name,
+              " must be [B, Cout, Hy, Wy]");
+}
+
+void conv3x3_fwd(const at::Tensor& x, const at::Tensor& w, const OptT& bias, at::Tensor& y, const OptT& am,
+                 int64_t pad, bool relu, int64_t pool) {
+  const sl::Conv2dShape s = conv_shape(x.sizes(), w.sizes(), pad, relu, pool);
+  conv_need(x, x, "x");
+  conv_need(w, x, "w");
+  conv_need(y, x, "y");
+  conv_check_y(y, s, "y");
+  const bool has_b = bias.has_value() && bias->defined();
+  if (has_b) {
+    conv_need(*bias, x, "bias");
+    TORCH_CHECK(bias->numel() == s.Cout, "bias [Cout]");
+  }
+  TORCH_CHECK((am.has_value() && am->defined()) == (bool)s.pool, "am goes with pooling");
+  if (s.pool) {
+    conv_need(*am, x, "am", true);
+    conv_check_y(*am, s, "am");
+  }
+  check(sl::conv3x3_fwd(x.data_ptr<float>(), w.data_ptr<float>(), has_b ? bias->data_ptr<float>() : nullptr,
+                        y.data_ptr<float>(), s.pool ? am->data_ptr<uint8_t>() : nullptr, s, cur_stream()),
+        "conv3x3_fwd");
+}
+
+// dy, y (, am) of the forward -> the operands of both backward kernels
+const uint8_t* conv_check_bwd(const at::Tensor& dy, const at::Tensor& y, const OptT& am, const at::Tensor& like,
+                              const sl::Conv2dShape& s) {
+  conv_need(dy, like, "dy");
+  conv_need(y, like, "y");
+  conv_check_y(dy, s, "dy");
+  conv_check_y(y, s, "y");
+  TORCH_CHECK((am.has_value() && am->defined()) == (bool)s.pool, "am goes with pooling");
+  if (!s.pool) return nullptr;
+  conv_need(*am, like, "am", true);
+  conv_check_y(*am, s, "am");
+  return am->data_ptr<uint8_t>();
+}
+
+void conv3x3_dgrad(const at::Tensor& dy, const at::Tensor& y, const OptT& am, const at::Tensor& w, at::Tensor& dx,
+                   int64_t pad, bool relu, int64_t pool) {
+  const sl::Conv2dShape s = conv_shape(dx.sizes(), w.sizes(), pad, relu, pool);
+  conv_need(w, dy, "w");
+  conv_need(dx, dy, "dx");
+  const uint8_t* a = conv_check_bwd(dy, y, am, dy, s);
+  check(sl::conv3x3_dgrad(dy.data_ptr<float>(), y.data_ptr<float>(), a, w.data_ptr<float>(), dx.data_ptr<float>(), s,
+                          cur_stream()),
+        "conv3x3_dgrad");
+}
+
+int64_t conv3x3_wgrad_ws(std::vector<int64_t> x_shape, std::vector<int64_t> w_shape, int64_t pad, int64_t pool) {
+  const sl::Conv2dShape s = conv_shape(x_shape, w_shape, pad, false, pool);
+  return (int64_t)sl::conv3x3_wgrad_slabs(s) * s.Cout * (s.Cin * 9 + 1);
+}
+
+void conv3x3_wgrad(const at::Tensor& dy, const at::Tensor& y, const OptT& am, const at::Tensor& x, at::Tensor& ws,
+                   at::Tensor& dw, const OptT& db, int64_t pad, bool relu, int64_t pool) {
+  const sl::Conv2dShape s = conv_shape(x.sizes(), dw.sizes(), pad, relu, pool);
+  conv_need(x, dy, "x");
+  conv_need(dw, dy, "dw");
+  conv_need(ws, dy, "workspace");
+  TORCH_CHECK(ws.numel() >= (int64_t)sl::conv3x3_wgrad_slabs(s) * s.Cout * (s.Cin * 9 + 1), "conv3x3_wgrad workspace");
+  const bool has_b = db.has_value() && db->defined();
+  if (has_b) {
+    conv_need(*db, dy, "db");
+    TORCH_CHECK(db->numel() == s.Cout, "db [Cout]");
+  }
+  const uint8_t* a = conv_check_bwd(dy, y, am, dy, s);
+  check(sl::conv3x3_wgrad(dy.data_ptr<float>(), y.data_ptr<float>(), a, x.data_ptr<float>(), ws.data_ptr<float>(),
+                          dw.data_ptr<float>(), has_b ? db->data_ptr<float>() : nullptr, s, cur_stream()),
+        "conv3x3_wgrad");
+}
+
 // ---------------------------------------------------------------- loss / metrics
 void softmax_ce(const at::Tensor& x, const at::Tensor& y, int64_t ignore, double scale, at::Tensor& loss_rows,
                 const OptT& d) {
@@ -831,6 +936,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("opt_flat", &opt_flat);
   m.def("multi_opt", &multi_opt);
   m.def("grad_norm", &grad_norm);
+  m.def("conv3x3_fwd", &conv3x3_fwd);
+  m.def("conv3x3_dgrad", &conv3x3_dgrad);
+  m.def("conv3x3_wgrad", &conv3x3_wgrad);
+  m.def("conv3x3_wgrad_ws", &conv3x3_wgrad_ws);
   m.attr("multi_opt_chunk") = (int64_t)sl::kMultiOptChunk;
   m.attr("multi_opt_max") = (int64_t)sl::kMultiOptMax;
   m.def("softmax_ce", &softmax_ce);

@@ -13,10 +13,14 @@ gradient-norm clipping), and any `torch.optim` optimizer works too:
   counter hash, so they are regenerated in backward instead of stored.
 * `FusedConvFront`: `model1_sisa`'s Conv2d(1,32,3) + ReLU + MaxPool(2) + flatten, with
   the uint8 gather fused into the forward (models.py:16-30).
+* `FusedConv2d`: `nn.Conv2d(in, out, 3, padding=0|1)` + optional ReLU + optional
+  MaxPool2d(2, 2) for any channel count and image size, as implicit-GEMM MFMA kernels.  The
+  output stays 4-D and the input gets a gradient when it requires one, so the layer can be
+  stacked or start a server part.  The un-pooled activation is never stored.
 * `softmax_cross_entropy`: mean CrossEntropyLoss as one fused forward+backward kernel.
 
 On CPU tensors the same layers run the eager torch implementations (ops/torch_ops.py),
-so a model is written once. State-dict keys match `nn.Linear` / `model1_sisa`.
+so a model is written once. State-dict keys match `nn.Linear` / `nn.Conv2d` / `model1_sisa`.
 """
 from __future__ import annotations
 
@@ -100,6 +104,79 @@ class FusedLinear(nn.Module):
                 f"relu={self.relu}, dropout={self.dropout}")
 
 
+class _Conv2dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, pad: int, relu: bool, pool):
+        K = ops.impl(x.device)
+        x = x.contiguous()
+        y, am = K.conv3x3_fwd(x, weight.detach(), bias.detach() if bias is not None else None, pad, relu, pool)
+        ctx.save_for_backward(x, weight, y, am)
+        ctx.pad, ctx.relu, ctx.pool, ctx.has_bias = pad, relu, pool, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, y, am = ctx.saved_tensors
+        K = ops.impl(dy.device)
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv3x3_dgrad(dy, y, am, weight.detach(), ctx.pad, ctx.relu, ctx.pool, x.shape)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = K.conv3x3_wgrad(dy, y, am, x, ctx.pad, ctx.relu, ctx.pool)
+        return dx, dw, (db if ctx.has_bias else None), None, None, None
+
+
+class FusedConv2d(nn.Module):
+    """`nn.Conv2d(in, out, 3, padding=padding)` [+ ReLU] [+ MaxPool2d(2, 2) with `pool=2`] as one
+    kernel per pass.  Input [B, Cin, H, W] float32, output [B, Cout, H', W'] (never flattened).
+    Parameters are named and initialised like `nn.Conv2d`'s.  Supported: kernel_size 3,
+    stride 1, padding 0 or 1, pool None or 2; anything else raises ValueError."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size=3, stride=1, padding=0,
+                 bias: bool = True, relu: bool = False, pool=None):
+        super().__init__()
+        if kernel_size not in (3, (3, 3), [3, 3]):
+            raise ValueError(f"FusedConv2d: kernel_size must be 3, got {kernel_size!r}")
+        if stride not in (1, (1, 1), [1, 1]):
+            raise ValueError(f"FusedConv2d: stride must be 1, got {stride!r}")
+        if padding not in (0, 1, (0, 0), (1, 1), [0, 0], [1, 1]):
+            raise ValueError(f"FusedConv2d: padding must be 0 or 1, got {padding!r}")
+        if pool not in (None, 2, (2, 2), [2, 2]):
+            raise ValueError(f"FusedConv2d: pool must be None or 2, got {pool!r}")
+        if in_channels < 1 or out_channels < 1:
+            raise ValueError("FusedConv2d: in_channels and out_channels must be >= 1")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.padding = padding if isinstance(padding, int) else int(padding[0])
+        self.relu, self.pool = bool(relu), (None if pool is None else 2)
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 3, 3))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        # nn.Conv2d's default init (kaiming-uniform a=sqrt(5), uniform bias over fan_in = Cin * 9)
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            bound = 1.0 / math.sqrt(self.in_channels * 9)
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x):
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f"FusedConv2d: expected [B, {self.in_channels}, H, W], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"FusedConv2d: input must be float32, got {x.dtype}")
+        ho, wo = x.shape[2] + 2 * self.padding - 2, x.shape[3] + 2 * self.padding - 2
+        if x.shape[2] < 3 or x.shape[3] < 3:
+            raise ValueError(f"FusedConv2d: input {tuple(x.shape[2:])} is smaller than the 3x3 kernel")
+        if self.pool and (ho < 2 or wo < 2):
+            raise ValueError(f"FusedConv2d: conv output {ho}x{wo} is smaller than the 2x2 pooling window")
+        return _Conv2dFn.apply(x, self.weight, self.bias, self.padding, self.relu, self.pool)
+
+    def extra_repr(self):
+        return (f"in_channels={self.in_channels}, out_channels={self.out_channels}, kernel_size=3, "
+                f"padding={self.padding}, relu={self.relu}, pool={self.pool}")
+
+
 class _ConvFrontFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -155,4 +232,4 @@ def softmax_cross_entropy(logits, labels, ignore_index: int = -100):
     return _SoftmaxCEFn.apply(logits, labels, ignore_index)
 
 
-__all__ = ["FusedLinear", "FusedConvFront", "softmax_cross_entropy"]
+__all__ = ["FusedLinear", "FusedConv2d", "FusedConvFront", "softmax_cross_entropy"]

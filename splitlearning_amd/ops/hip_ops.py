@@ -187,6 +187,40 @@ def conv_local_epoch_multi_(items, B: int, cfg):
 _TABLE: dict = {}
 
 
+# ---------------------------------------------------------------- general 3x3 conv
+# csrc/conv2d.hip: implicit-GEMM Conv2d(3x3, stride 1, padding 0 | 1) [+ ReLU] [+ MaxPool2d(2, 2)].
+# The un-pooled activation and the conv-resolution gradient are never stored.
+def _conv_y_shape(x_shape, cout: int, pad: int, pool):
+    ho, wo = x_shape[2] + 2 * pad - 2, x_shape[3] + 2 * pad - 2
+    return (x_shape[0], cout, ho // 2, wo // 2) if pool else (x_shape[0], cout, ho, wo)
+
+
+def conv3x3_fwd(x, w, b, pad: int, relu: bool, pool):
+    """(y, am): am = uint8 window position 2*dy + dx of the maximum, None without pooling."""
+    shape = _conv_y_shape(x.shape, w.shape[0], pad, pool)
+    y = torch.empty(shape, device=x.device, dtype=torch.float32)
+    am = torch.empty(shape, device=x.device, dtype=torch.uint8) if pool else None
+    C().conv3x3_fwd(x, w.detach(), b.detach() if b is not None else None, y, am, int(pad), bool(relu), int(pool or 0))
+    return y, am
+
+
+def conv3x3_dgrad(dy, y, am, w, pad: int, relu: bool, pool, x_shape):
+    dx = torch.empty(tuple(x_shape), device=dy.device, dtype=torch.float32)
+    C().conv3x3_dgrad(dy, y, am, w.detach(), dx, int(pad), bool(relu), int(pool or 0))
+    return dx
+
+
+def conv3x3_wgrad(dy, y, am, x, pad: int, relu: bool, pool):
+    """(dw, db); the reduction over pixels runs in slabs summed in a fixed order (bitwise
+    reproducible)."""
+    w_shape = (dy.shape[1], x.shape[1], 3, 3)
+    dw = torch.empty(w_shape, device=dy.device, dtype=torch.float32)
+    db = torch.empty(w_shape[0], device=dy.device, dtype=torch.float32)
+    ws = _workspace(dy.device, C().conv3x3_wgrad_ws(list(x.shape), list(w_shape), int(pad), int(pool or 0)), "conv2d")
+    C().conv3x3_wgrad(dy, y, am, x, ws, dw, db, int(pad), bool(relu), int(pool or 0))
+    return dw, db
+
+
 # ---------------------------------------------------------------- linear
 # training batches (M <= 128) run the skinny split-K kernels.  Many rows (evaluation over a
 # test set, large batches): the forward product runs the in-tree LDS-tiled MFMA GEMM

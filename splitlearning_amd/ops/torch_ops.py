@@ -53,6 +53,52 @@ def conv_front_bwd(dy, y, am, x_u8, idx, w, b):
     return dw, db
 
 
+# ---------------------------------------------------------------- general 3x3 conv
+def conv3x3_fwd(x, w, b, pad: int, relu: bool, pool):
+    """Conv2d(3x3, stride 1, padding `pad`) [+ ReLU] [+ MaxPool2d(2, 2) when `pool` == 2].
+
+    Returns (y [B,Cout,Hy,Wy], am): am is uint8 like y, the window position 2*dy + dx of the
+    maximum (a tie goes to the lowest position), or None without pooling."""
+    z = F.conv2d(x, w, b, padding=pad)
+    if relu:
+        z = F.relu(z)
+    if not pool:
+        return z, None
+    y, ind = F.max_pool2d(z, 2, 2, return_indices=True)
+    wo = z.shape[-1]           # ind is the flat index into the Ho x Wo plane
+    am = (((ind // wo) % 2) * 2 + (ind % wo) % 2).to(torch.uint8)
+    return y, am
+
+
+def _conv3x3_dz(dy, y, am, relu: bool, pool, ho: int, wo: int):
+    """The gradient at conv resolution: dy routed to each window's maximum, masked by the ReLU;
+    0 in the row / column the floor rule leaves out of every window."""
+    g = dy * (y > 0) if relu else dy
+    if not pool:
+        return g
+    B, C, hp, wp = dy.shape
+    a = am.long()
+    rr = 2 * torch.arange(hp, device=dy.device).view(1, 1, hp, 1) + a // 2
+    cc = 2 * torch.arange(wp, device=dy.device).view(1, 1, 1, wp) + a % 2
+    dz = torch.zeros(B, C, ho * wo, dtype=dy.dtype, device=dy.device)
+    dz.scatter_(2, (rr * wo + cc).reshape(B, C, -1), g.reshape(B, C, -1))
+    return dz.view(B, C, ho, wo)
+
+
+def conv3x3_dgrad(dy, y, am, w, pad: int, relu: bool, pool, x_shape):
+    ho, wo = x_shape[2] + 2 * pad - 2, x_shape[3] + 2 * pad - 2
+    dz = _conv3x3_dz(dy, y, am, relu, pool, ho, wo)
+    return torch.nn.grad.conv2d_input(tuple(x_shape), w, dz, padding=pad)
+
+
+def conv3x3_wgrad(dy, y, am, x, pad: int, relu: bool, pool):
+    """(dw [Cout,Cin,3,3], db [Cout])."""
+    ho, wo = x.shape[2] + 2 * pad - 2, x.shape[3] + 2 * pad - 2
+    dz = _conv3x3_dz(dy, y, am, relu, pool, ho, wo)
+    dw = torch.nn.grad.conv2d_weight(x, (dy.shape[1], x.shape[1], 3, 3), dz, padding=pad)
+    return dw, dz.sum(dim=(0, 2, 3))
+
+
 # ---------------------------------------------------------------- linear
 # `--dtype bf16`: GEMM operands rounded to bf16, fp32 accumulation (the HIP kernels' rule,
 # csrc/common.h bfr); parameters and optimizer state stay fp32

@@ -64,6 +64,7 @@ class Watchdog:
         self.logger = logger
         self.fault = fault
         self.failed: str | None = None
+        self._failing = False
         self._count = 0
         self._published = -1
         self._tag = "start"
@@ -193,9 +194,9 @@ class Watchdog:
         return ranks
 
     def _fail(self, kind: str, msg: str):
-        if self.failed:
+        if self.failed or self._failing:
             return
-        self.failed = kind
+        self._failing = True
         rep = {"kind": kind, "message": msg, "reporter": self.rank, "ranks": self.report()}
         self._say(f"{kind}: {msg}; last phase per rank: " +
                   ", ".join(f"{r}={d['last_phase']}" for r, d in rep["ranks"].items()))
@@ -206,6 +207,8 @@ class Watchdog:
                     json.dump(rep, f, indent=1)
             except OSError:
                 pass
+        # published last: whoever sees `failed` set finds the report complete on disk
+        self.failed = kind
         if self.policy == "abort":
             sys.stdout.flush()
             sys.stderr.flush()
