@@ -20,6 +20,7 @@
 #include "host.h"
 #include "optim.h"
 #include "conv2d.h"
+#include "groupnorm.h"
 
 namespace sl {
 hipError_t conv_fwd(const void* x, bool x_u8, const int64_t* idx, int64_t row0, int B, const float* w,
@@ -744,6 +745,106 @@ void conv3x3_wgrad(const at::Tensor& dy, const at::Tensor& y, const OptT& am, co
         "conv3x3_wgrad");
 }
 
+// ---------------------------------------------------------------- GroupNorm (groupnorm.hip)
+// x / dx [B, C, *], y / dy / am [B, C, *] or [B, C, H / 2, W / 2] with pooling, mean / rstd [B, G],
+// w / b / dw / db [C] (all four absent without the affine): contiguous, fp32 (am uint8), on the
+// current device, each under 2 GB.
+sl::GroupNormShape gn_shape(at::IntArrayRef x, int64_t groups, double eps, bool relu, int64_t pool) {
+  TORCH_CHECK(x.size() >= 2, "group_norm: x [B, C, *]");
+  TORCH_CHECK(pool == 0 || pool == 2, "group_norm: pool 0 (none) or 2");
+  TORCH_CHECK(groups >= 1 && x[1] >= 1 && x[1] % groups == 0, "group_norm: C must be a multiple of the groups");
+  int64_t L = 1;
+  for (size_t i = 2; i < x.size(); ++i) L *= x[i];
+  TORCH_CHECK(x[0] >= 1 && L >= 1, "group_norm: empty input");
+  TORCH_CHECK(x[0] * x[1] * L < (int64_t(1) << 29), "group_norm: input too large");
+  sl::GroupNormShape s{};
+  s.B = (int)x[0], s.C = (int)x[1], s.G = (int)groups, s.L = (int)L;
+  s.relu = relu, s.pool = pool == 2, s.eps = (float)eps;
+  if (s.pool) {
+    TORCH_CHECK(x.size() == 4 && x[2] >= 2 && x[3] >= 2, "group_norm: pooling needs [B, C, H, W] with H, W >= 2");
+    s.H = (int)x[2], s.W = (int)x[3], s.Hy = s.H / 2, s.Wy = s.W / 2;
+  }
+  return s;
+}
+
+void gn_check_y(const at::Tensor& t, const at::Tensor& x, const sl::GroupNormShape& s, const char* name, bool u8) {
+  conv_need(t, x, name, u8);
+  if (s.pool) {
+    TORCH_CHECK(t.dim() == 4 && t.size(0) == s.B && t.size(1) == s.C && t.size(2) == s.Hy && t.size(3) == s.Wy, name,
+                " must be [B, C, H / 2, W / 2]");
+  } else {
+    TORCH_CHECK(t.sizes() == x.sizes(), name, " must have x's shape");
+  }
+}
+
+void gn_check_vec(const at::Tensor& t, const at::Tensor& x, int64_t numel, const char* name) {
+  conv_need(t, x, name);
+  TORCH_CHECK(t.numel() == numel, name, " has the wrong number of elements");
+}
+
+// the affine's two vectors: both or neither
+bool gn_affine(const OptT& w, const OptT& b, const at::Tensor& x, int C, const char* wn, const char* bn) {
+  const bool has_w = w.has_value() && w->defined(), has_b = b.has_value() && b->defined();
+  TORCH_CHECK(has_w == has_b, "group_norm: ", wn, " and ", bn, " go together");
+  if (has_w) {
+    gn_check_vec(*w, x, C, wn);
+    gn_check_vec(*b, x, C, bn);
+  }
+  return has_w;
+}
+
+const uint8_t* gn_check_am(const OptT& am, const at::Tensor& x, const sl::GroupNormShape& s) {
+  TORCH_CHECK((am.has_value() && am->defined()) == (bool)s.pool, "am goes with pooling");
+  if (!s.pool) return nullptr;
+  gn_check_y(*am, x, s, "am", true);
+  return am->data_ptr<uint8_t>();
+}
+
+void group_norm_fwd(const at::Tensor& x, const OptT& w, const OptT& b, at::Tensor& y, at::Tensor& mean,
+                    at::Tensor& rstd, const OptT& am, int64_t groups, double eps, bool relu, int64_t pool) {
+  const sl::GroupNormShape s = gn_shape(x.sizes(), groups, eps, relu, pool);
+  conv_need(x, x, "x");
+  gn_check_y(y, x, s, "y", false);
+  gn_check_vec(mean, x, (int64_t)s.B * s.G, "mean");
+  gn_check_vec(rstd, x, (int64_t)s.B * s.G, "rstd");
+  const bool affine = gn_affine(w, b, x, s.C, "weight", "bias");
+  const uint8_t* a = gn_check_am(am, x, s);
+  check(sl::group_norm_fwd(x.data_ptr<float>(), affine ? w->data_ptr<float>() : nullptr,
+                           affine ? b->data_ptr<float>() : nullptr, y.data_ptr<float>(), mean.data_ptr<float>(),
+                           rstd.data_ptr<float>(), const_cast<uint8_t*>(a), s, cur_stream()),
+        "group_norm_fwd");
+}
+
+void group_norm_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& mean, const at::Tensor& rstd,
+                    const OptT& w, const OptT& b, const OptT& am, const OptT& dx, const OptT& ws, const OptT& dw,
+                    const OptT& db, int64_t groups, bool relu, int64_t pool) {
+  const sl::GroupNormShape s = gn_shape(x.sizes(), groups, 0.0, relu, pool);
+  conv_need(x, x, "x");
+  gn_check_y(dy, x, s, "dy", false);
+  gn_check_vec(mean, x, (int64_t)s.B * s.G, "mean");
+  gn_check_vec(rstd, x, (int64_t)s.B * s.G, "rstd");
+  const bool affine = gn_affine(w, b, x, s.C, "weight", "bias");
+  TORCH_CHECK(gn_affine(dw, db, x, s.C, "dweight", "dbias") == affine, "group_norm: dweight / dbias go with the affine");
+  const bool has_ws = ws.has_value() && ws->defined();
+  TORCH_CHECK(has_ws == affine, "group_norm: the workspace goes with the affine");
+  if (affine) {
+    conv_need(*ws, x, "workspace");
+    TORCH_CHECK(ws->numel() >= (int64_t)s.B * s.C * 2, "group_norm workspace: [B, C, 2]");
+  }
+  const bool need_dx = dx.has_value() && dx->defined();
+  if (need_dx) {
+    conv_need(*dx, x, "dx");
+    TORCH_CHECK(dx->sizes() == x.sizes(), "dx must have x's shape");
+  }
+  const uint8_t* a = gn_check_am(am, x, s);
+  check(sl::group_norm_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                           affine ? w->data_ptr<float>() : nullptr, affine ? b->data_ptr<float>() : nullptr, a,
+                           need_dx ? dx->data_ptr<float>() : nullptr, affine ? ws->data_ptr<float>() : nullptr,
+                           affine ? dw->data_ptr<float>() : nullptr, affine ? db->data_ptr<float>() : nullptr, s,
+                           cur_stream()),
+        "group_norm_bwd");
+}
+
 // ---------------------------------------------------------------- loss / metrics
 void softmax_ce(const at::Tensor& x, const at::Tensor& y, int64_t ignore, double scale, at::Tensor& loss_rows,
                 const OptT& d) {
@@ -940,6 +1041,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv3x3_dgrad", &conv3x3_dgrad);
   m.def("conv3x3_wgrad", &conv3x3_wgrad);
   m.def("conv3x3_wgrad_ws", &conv3x3_wgrad_ws);
+  m.def("group_norm_fwd", &group_norm_fwd);
+  m.def("group_norm_bwd", &group_norm_bwd);
   m.attr("multi_opt_chunk") = (int64_t)sl::kMultiOptChunk;
   m.attr("multi_opt_max") = (int64_t)sl::kMultiOptMax;
   m.def("softmax_ce", &softmax_ce);

@@ -17,10 +17,15 @@ gradient-norm clipping), and any `torch.optim` optimizer works too:
   MaxPool2d(2, 2) for any channel count and image size, as implicit-GEMM MFMA kernels.  The
   output stays 4-D and the input gets a gradient when it requires one, so the layer can be
   stacked or start a server part.  The un-pooled activation is never stored.
+* `FusedGroupNorm`: `nn.GroupNorm(groups, channels)` + optional ReLU + optional MaxPool2d(2, 2)
+  as one kernel per pass, for any [B, C, *] input.  After a `FusedConv2d` it makes conv, norm,
+  ReLU and pool two kernels per direction with no un-pooled activation stored.  It keeps no
+  buffers, so weight relay, snapshots and unlearning carry a model that uses it as they are.
 * `softmax_cross_entropy`: mean CrossEntropyLoss as one fused forward+backward kernel.
 
 On CPU tensors the same layers run the eager torch implementations (ops/torch_ops.py),
-so a model is written once. State-dict keys match `nn.Linear` / `nn.Conv2d` / `model1_sisa`.
+so a model is written once. State-dict keys match `nn.Linear` / `nn.Conv2d` / `nn.GroupNorm` /
+`model1_sisa`.
 """
 from __future__ import annotations
 
@@ -177,6 +182,75 @@ class FusedConv2d(nn.Module):
                 f"padding={self.padding}, relu={self.relu}, pool={self.pool}")
 
 
+class _GroupNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups: int, eps: float, relu: bool, pool):
+        K = ops.impl(x.device)
+        x = x.contiguous()
+        affine = weight is not None
+        y, mean, rstd, am = K.group_norm_fwd(x, weight.detach() if affine else None, bias.detach() if affine else None,
+                                             groups, eps, relu, pool)
+        # y is not saved: the backward recomputes the pre-activation from x, mean and rstd
+        ctx.save_for_backward(x, mean, rstd, am, weight, bias)
+        ctx.groups, ctx.relu, ctx.pool = groups, relu, pool
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd, am, weight, bias = ctx.saved_tensors
+        K = ops.impl(dy.device)
+        affine = weight is not None
+        dx, dw, db = K.group_norm_bwd(dy.contiguous(), x, mean, rstd, weight.detach() if affine else None,
+                                      bias.detach() if affine else None, am, ctx.groups, ctx.relu, ctx.pool,
+                                      ctx.needs_input_grad[0])
+        return dx, dw, db, None, None, None, None
+
+
+class FusedGroupNorm(nn.Module):
+    """`nn.GroupNorm(num_groups, num_channels, eps, affine)` [+ ReLU] [+ MaxPool2d(2, 2) with
+    `pool=2`] as one kernel per pass (plus the per-channel sum of the parameter gradients).
+    Input [B, C, *] float32; output [B, C, *], or [B, C, H // 2, W // 2] with pooling, which needs
+    a 4-D input with H, W >= 2 (an odd last row or column is left out of the output and still
+    counts in the statistics).  Parameters are named and initialised like `nn.GroupNorm`'s; there
+    are no buffers, and `train()` and `eval()` compute the same."""
+
+    def __init__(self, num_groups: int, num_channels: int, eps: float = 1e-5, affine: bool = True,
+                 relu: bool = False, pool=None):
+        super().__init__()
+        if num_groups < 1 or num_channels < 1 or num_channels % num_groups != 0:
+            raise ValueError(f"FusedGroupNorm: num_channels ({num_channels}) must be a positive multiple of "
+                             f"num_groups ({num_groups})")
+        if pool not in (None, 2):
+            raise ValueError(f"FusedGroupNorm: pool must be None or 2, got {pool!r}")
+        self.num_groups, self.num_channels, self.eps, self.affine = num_groups, num_channels, float(eps), bool(affine)
+        self.relu, self.pool = bool(relu), pool
+        if self.affine:
+            self.weight = nn.Parameter(torch.empty(num_channels))
+            self.bias = nn.Parameter(torch.empty(num_channels))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        if self.affine:
+            nn.init.ones_(self.weight)
+            nn.init.zeros_(self.bias)
+
+    def forward(self, x):
+        if x.dim() < 2 or x.shape[1] != self.num_channels:
+            raise ValueError(f"FusedGroupNorm: expected [B, {self.num_channels}, *], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"FusedGroupNorm: input must be float32, got {x.dtype}")
+        if self.pool and (x.dim() != 4 or x.shape[2] < 2 or x.shape[3] < 2):
+            raise ValueError(f"FusedGroupNorm: pool=2 needs [B, C, H, W] with H, W >= 2, got {tuple(x.shape)}")
+        return _GroupNormFn.apply(x, self.weight, self.bias, self.num_groups, self.eps, self.relu, self.pool)
+
+    def extra_repr(self):
+        return (f"{self.num_groups}, {self.num_channels}, eps={self.eps}, affine={self.affine}, "
+                f"relu={self.relu}, pool={self.pool}")
+
+
 class _ConvFrontFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -232,4 +306,4 @@ def softmax_cross_entropy(logits, labels, ignore_index: int = -100):
     return _SoftmaxCEFn.apply(logits, labels, ignore_index)
 
 
-__all__ = ["FusedLinear", "FusedConv2d", "FusedConvFront", "softmax_cross_entropy"]
+__all__ = ["FusedLinear", "FusedConv2d", "FusedGroupNorm", "FusedConvFront", "softmax_cross_entropy"]

@@ -221,6 +221,37 @@ def conv3x3_wgrad(dy, y, am, x, pad: int, relu: bool, pool):
     return dw, db
 
 
+# ---------------------------------------------------------------- GroupNorm
+# csrc/groupnorm.hip: GroupNorm [+ ReLU] [+ MaxPool2d(2, 2)], one workgroup per (sample, group).
+def group_norm_fwd(x, weight, bias, groups: int, eps: float, relu: bool, pool):
+    """(y, mean [B, G], rstd [B, G], am): am = uint8 window position 2*dy + dx of the maximum,
+    None without pooling."""
+    shape = (x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2) if pool else tuple(x.shape)
+    y = torch.empty(shape, device=x.device, dtype=torch.float32)
+    mean = torch.empty(x.shape[0], groups, device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    am = torch.empty(shape, device=x.device, dtype=torch.uint8) if pool else None
+    affine = weight is not None
+    C().group_norm_fwd(x, weight.detach() if affine else None, bias.detach() if affine else None, y, mean, rstd, am,
+                       int(groups), float(eps), bool(relu), int(pool or 0))
+    return y, mean, rstd, am
+
+
+def group_norm_bwd(dy, x, mean, rstd, weight, bias, am, groups: int, relu: bool, pool, need_dx: bool = True):
+    """(dx, dweight, dbias); dx is None when `need_dx` is false, dweight / dbias without the
+    affine.  Every sum runs in a fixed order (bitwise reproducible)."""
+    affine = weight is not None
+    dx = torch.empty_like(x) if need_dx else None
+    dw = db = ws = None
+    if affine:
+        dw = torch.empty(x.shape[1], device=x.device, dtype=torch.float32)
+        db = torch.empty_like(dw)
+        ws = _workspace(x.device, 2 * x.shape[0] * x.shape[1], "groupnorm")
+    C().group_norm_bwd(dy, x, mean, rstd, weight.detach() if affine else None, bias.detach() if affine else None, am,
+                       dx, ws, dw, db, int(groups), bool(relu), int(pool or 0))
+    return dx, dw, db
+
+
 # ---------------------------------------------------------------- linear
 # training batches (M <= 128) run the skinny split-K kernels.  Many rows (evaluation over a
 # test set, large batches): the forward product runs the in-tree LDS-tiled MFMA GEMM

@@ -99,6 +99,61 @@ def conv3x3_wgrad(dy, y, am, x, pad: int, relu: bool, pool):
     return dw, dz.sum(dim=(0, 2, 3))
 
 
+# ---------------------------------------------------------------- GroupNorm
+def _gn_pre(x, mean, rstd, weight, bias, groups: int):
+    """(xh, z): xh = (x - mean) * rstd per (sample, group), z = xh * weight[c] + bias[c]."""
+    B, C = x.shape[:2]
+    xh = ((x.reshape(B, groups, -1) - mean.unsqueeze(-1)) * rstd.unsqueeze(-1)).reshape(x.shape)
+    if weight is None:
+        return xh, xh
+    cshape = (1, C) + (1,) * (x.dim() - 2)
+    return xh, xh * weight.reshape(cshape) + bias.reshape(cshape)
+
+
+def group_norm_fwd(x, weight, bias, groups: int, eps: float, relu: bool, pool):
+    """GroupNorm(groups, C, eps) [+ ReLU] [+ MaxPool2d(2, 2) when `pool` == 2] of x [B, C, *].
+
+    Returns (y, mean [B, G], rstd [B, G], am): the variance is the mean squared deviation from
+    the mean (two passes); am is uint8 like y, the window position 2*dy + dx of the maximum (a
+    tie goes to the lowest position), or None without pooling."""
+    B = x.shape[0]
+    xg = x.reshape(B, groups, -1)
+    mean = xg.mean(dim=2)
+    var = (xg - mean.unsqueeze(-1)).square().mean(dim=2)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    z = _gn_pre(x, mean, rstd, weight, bias, groups)[1]
+    if relu:
+        z = F.relu(z)
+    if not pool:
+        return z, mean, rstd, None
+    y, ind = F.max_pool2d(z, 2, 2, return_indices=True)
+    wo = z.shape[-1]           # ind is the flat index into the H x W plane
+    am = (((ind // wo) % 2) * 2 + (ind % wo) % 2).to(torch.uint8)
+    return y, mean, rstd, am
+
+
+def group_norm_bwd(dy, x, mean, rstd, weight, bias, am, groups: int, relu: bool, pool, need_dx: bool = True):
+    """(dx, dweight, dbias) by the explicit formula: dz = dy routed back through the pool and
+    the ReLU, xh = (x - mean) * rstd, dweight[c] = sum dz * xh, dbias[c] = sum dz, and per
+    (sample, group) of n elements dx = rstd * (w dz - mean_n(w dz) - xh * mean_n(w dz xh)).
+    dx is None when `need_dx` is false; dweight and dbias are None without the affine."""
+    B, C = x.shape[:2]
+    xh, z = _gn_pre(x, mean, rstd, weight, bias, groups)
+    dz = _conv3x3_dz(dy, None, am, False, pool, x.shape[2], x.shape[3]) if pool else dy
+    if relu:
+        dz = dz * (z > 0)
+    dweight = dbias = dx = None
+    red = (0,) + tuple(range(2, x.dim()))
+    if weight is not None:
+        dweight, dbias = (dz * xh).sum(dim=red), dz.sum(dim=red)
+    if need_dx:
+        wdz = dz if weight is None else dz * weight.reshape((1, C) + (1,) * (x.dim() - 2))
+        wg, xg = wdz.reshape(B, groups, -1), xh.reshape(B, groups, -1)
+        m1, m2 = wg.mean(dim=2, keepdim=True), (wg * xg).mean(dim=2, keepdim=True)
+        dx = (rstd.unsqueeze(-1) * (wg - m1 - xg * m2)).reshape(x.shape)
+    return dx, dweight, dbias
+
+
 # ---------------------------------------------------------------- linear
 # `--dtype bf16`: GEMM operands rounded to bf16, fp32 accumulation (the HIP kernels' rule,
 # csrc/common.h bfr); parameters and optimizer state stay fp32
