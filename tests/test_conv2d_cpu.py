@@ -21,9 +21,16 @@ SHAPES = [
     (3, 8, 64, 16, 16, 1, 2),       # several M tiles
     (16, 1, 32, 28, 28, 0, 2),      # the MNIST front
     (64, 8, 16, 12, 12, 1, None),   # 9216 pixels to reduce: several wgrad slabs
+    # past one 64 x 64 tile of csrc/conv2d.hip (blockIdx.y > 0 in fwd / dgrad, blockIdx.x > 0 in wgrad)
+    (1, 2, 65, 4, 4, 1, 2),         # fwd second N tile holding one channel; wgrad second M tile
+    (1, 65, 3, 5, 5, 0, None),      # dgrad second N tile holding one channel; fwd K = 585; wgrad 10 N tiles
+    (2, 70, 130, 6, 6, 1, 2),       # both at once: three fwd N tiles, three wgrad M tiles, padding, pooling
+    (1, 3, 129, 3, 3, 0, None),     # one output pixel per sample under three N tiles
 ]
-# (index into SHAPES, relu): every shape with ReLU, shapes 2 and 4 (1-based) also without
-INT_CASES = [(i, True) for i in range(len(SHAPES))] + [(1, False), (3, False)]
+# (index into SHAPES, relu): every shape with ReLU, shapes 2, 4, 9 and 11 (1-based) also without
+INT_CASES = [(i, True) for i in range(len(SHAPES))] + [(1, False), (3, False), (8, False), (10, False)]
+# (index into SHAPES, relu) run again with bias=False: one pooled and one un-pooled shape past one tile
+NO_BIAS_CASES = [(10, True), (9, True)]
 SEED = 0
 
 
@@ -31,20 +38,21 @@ def torch_ref(x, w, b, g, pad, relu, pool):
     """nn.Conv2d [+ ReLU] [+ MaxPool2d(2, 2)] and its autograd -> (y, dx, dw, db)."""
     x = x.detach().clone().requires_grad_(True)
     w = w.detach().clone().requires_grad_(True)
-    b = b.detach().clone().requires_grad_(True)
+    b = None if b is None else b.detach().clone().requires_grad_(True)
     y = F.conv2d(x, w, b, padding=pad)
     if relu:
         y = F.relu(y)
     if pool:
         y = F.max_pool2d(y, 2, 2)
     y.backward(g)
-    return y.detach(), x.grad, w.grad, b.grad
+    return y.detach(), x.grad, w.grad, None if b is None else b.grad
 
 
 @functools.lru_cache(maxsize=None)
-def int_case(i, relu):
+def int_case(i, relu, bias=True):
     """Small-integer inputs (every partial sum is an integer far below 2^24, so the result does
-    not depend on the summation order) and torch's CPU result, computed once and shared."""
+    not depend on the summation order) and torch's CPU result, computed once and shared.
+    `bias=False` draws the same x, w and g and drops b (b and db are None)."""
     B, cin, cout, H, W, pad, pool = SHAPES[i]
     gen = torch.Generator().manual_seed(SEED + i)
     x = torch.randint(0, 4, (B, cin, H, W), generator=gen).float()
@@ -53,30 +61,37 @@ def int_case(i, relu):
     ho, wo = H + 2 * pad - 2, W + 2 * pad - 2
     yshape = (B, cout, ho // 2, wo // 2) if pool else (B, cout, ho, wo)
     g = torch.randint(-2, 3, yshape, generator=gen).float()
+    b = b if bias else None
     y, dx, dw, db = torch_ref(x, w, b, g, pad, relu, pool)
     return dict(x=x, w=w, b=b, g=g, y=y, dx=dx, dw=dw, db=db, pad=pad, relu=relu, pool=pool)
 
 
 def make_layer(c, device):
-    layer = snn.FusedConv2d(c["w"].shape[1], c["w"].shape[0], padding=c["pad"], relu=c["relu"], pool=c["pool"])
+    layer = snn.FusedConv2d(c["w"].shape[1], c["w"].shape[0], padding=c["pad"], bias=c["b"] is not None,
+                            relu=c["relu"], pool=c["pool"])
     with torch.no_grad():
         layer.weight.copy_(c["w"])
-        layer.bias.copy_(c["b"])
+        if c["b"] is not None:
+            layer.bias.copy_(c["b"])
     return layer.to(device)
 
 
 def run_layer(c, device, x=None, x_grad=True):
-    """(y, dx, dw, db) of FusedConv2d on `device` for the case's inputs, moved to the CPU."""
+    """(y, dx, dw, db) of FusedConv2d on `device` for the case's inputs, moved to the CPU; db is
+    None for a case without bias."""
     layer = make_layer(c, device)
     x = (c["x"].to(device) if x is None else x).detach().clone().requires_grad_(x_grad)
     y = layer(x)
     y.backward(c["g"].to(device))
     cpu = lambda t: None if t is None else t.detach().cpu()
-    return cpu(y), cpu(x.grad), cpu(layer.weight.grad), cpu(layer.bias.grad)
+    return cpu(y), cpu(x.grad), cpu(layer.weight.grad), cpu(None if layer.bias is None else layer.bias.grad)
 
 
 def assert_case_equal(got, c):
     for name, t in zip(("y", "dx", "dw", "db"), got):
+        if c[name] is None:
+            assert t is None, name
+            continue
         assert torch.equal(t, c[name]), f"{name} differs: max |diff| {(t - c[name]).abs().max().item()}"
 
 
@@ -92,6 +107,20 @@ def test_integer_cases_are_exact_in_fp32_and_not_trivial(i, relu):
 @pytest.mark.parametrize("i,relu", INT_CASES)
 def test_integer_exact_on_torch_ops(i, relu):
     c = int_case(i, relu)
+    assert_case_equal(run_layer(c, "cpu"), c)
+
+
+@pytest.mark.parametrize("i,relu", NO_BIAS_CASES)
+def test_integer_exact_without_bias(i, relu):
+    c, cb = int_case(i, relu, bias=False), int_case(i, relu)
+    assert c["b"] is None and c["db"] is None
+    assert all(torch.equal(c[k], cb[k]) for k in ("x", "w", "g"))          # the draw order is the biased case's
+    ref64 = torch_ref(c["x"].double(), c["w"].double(), None, c["g"].double(), c["pad"], relu, c["pool"])
+    for name, t64 in zip(("y", "dx", "dw"), ref64):
+        assert torch.equal(c[name].double(), t64), name
+        assert c[name].abs().max() > 0, f"{name} is all zero: pick another seed"
+    assert not torch.equal(c["y"], cb["y"])                                 # the bias mattered
+    assert make_layer(c, "cpu").bias is None
     assert_case_equal(run_layer(c, "cpu"), c)
 
 

@@ -1,4 +1,6 @@
-"""FusedConv2d on an MI355X: the implicit-GEMM kernels of csrc/conv2d.hip against torch."""
+"""FusedConv2d on an MI355X: the implicit-GEMM kernels of csrc/conv2d.hip against torch.
+SHAPES[8:] exist for the launch geometry past one 64 x 64 tile: blockIdx.y > 0 in the forward (Cout > 64) and
+in dgrad (Cin > 64), blockIdx.x > 0 and more than three N tiles in wgrad; keep them in any edit of the table."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -7,7 +9,8 @@ from torch import nn
 from splitlearning_amd import nn as snn
 from splitlearning_amd.ops import hip_ops, torch_ops
 from splitlearning_amd.optim import FusedAdam
-from test_conv2d_cpu import INT_CASES, SHAPES, assert_case_equal, int_case, make_layer, run_layer, torch_ref
+from test_conv2d_cpu import (INT_CASES, NO_BIAS_CASES, SHAPES, assert_case_equal, int_case, make_layer, run_layer,
+                             torch_ref)
 from test_optim_cpu import assert_params_close
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +32,30 @@ def test_argmax_positions_match_torch(cuda, i):
     ry, ram = torch_ops.conv3x3_fwd(c["x"], c["w"], c["b"], c["pad"], True, 2)
     assert am.dtype == torch.uint8 and am.shape == y.shape
     assert torch.equal(y.cpu(), ry) and torch.equal(am.cpu(), ram)
+
+
+@pytest.mark.parametrize("i,relu", NO_BIAS_CASES)
+def test_integer_exact_without_bias(cuda, i, relu):
+    """bias=False: the null bias of the forward epilogue through the layer, and the null db of
+    conv_wgrad_sum_kernel through the binding (the layer's op always passes a db buffer)."""
+    c = int_case(i, relu, bias=False)
+    assert c["b"] is None and c["db"] is None
+    for name in ("y", "dx", "dw"):
+        assert c[name].abs().max() > 0, name
+    assert make_layer(c, cuda).bias is None
+    got = run_layer(c, cuda)
+    assert got[3] is None
+    assert_case_equal(got, c)
+    # the same weight gradient with no db to write
+    x, g, w = c["x"].to(cuda), c["g"].to(cuda), c["w"].to(cuda)
+    pool = int(c["pool"] or 0)
+    y, am = hip_ops.conv3x3_fwd(x, w, None, c["pad"], relu, c["pool"])
+    assert torch.equal(y.cpu(), c["y"])
+    n = hip_ops.C().conv3x3_wgrad_ws(list(x.shape), list(w.shape), c["pad"], pool)
+    ws = torch.empty(n, device=cuda)
+    dw = torch.full_like(w, float("nan"))
+    hip_ops.C().conv3x3_wgrad(g, y, am, x, ws, dw, None, c["pad"], relu, pool)
+    assert torch.equal(dw.cpu(), c["dw"])
 
 
 def test_all_equal_windows_route_to_position_zero(cuda):
@@ -75,7 +102,7 @@ def _float_run(mod, x, g, relu, pool):
     return y.detach(), x.grad, mod.weight.grad, mod.bias.grad
 
 
-@pytest.mark.parametrize("i", [3, 4, 5])
+@pytest.mark.parametrize("i", [3, 4, 5, 10])
 def test_random_floats_match_nn_conv2d(cuda, i):
     B, cin, cout, H, W, pad, pool = SHAPES[i]
     torch.manual_seed(10 + i)

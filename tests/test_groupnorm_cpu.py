@@ -22,11 +22,16 @@ SHAPES = [
     (1, 32, 1, (64, 64), None),     # S6 n = 131072: the span cannot stay on-chip
     (16, 100, 4, (), None),         # S7 2-D input, n = 25
     (4, 6, 2, (10,), None),         # S8 3-D input
+    # the two span forms of csrc/groupnorm.hip (in LDS while n + 3 <= 16000 floats, else re-read)
+    (2, 4, 2, (91, 89), 2),         # S9 n = 16198: re-read form with pooling, odd H and W, spans 8 bytes off
+    (2, 34, 2, (941,), None),       # S10 n = 15997: the largest LDS span, phases 0..3, 17 channels per group
+    (2, 4, 2, (7999,), None),       # S11 n = 15998: one float more, the re-read form at odd phases
+    (2, 10, 2, (6, 7), 2),          # S12 pooling with 5 channels per group (a wave's second channel), dropped column
 ]
 EPS = 1e-5
 # One seed per shape for the random-float cases: chosen so that no ReLU or argmax decision of the
 # float64 reference is closer than 1e-6 (decision_margins, asserted where the cases are used).
-SEEDS = [0, 1, 2, 3, 20, 13, 6, 7]
+SEEDS = [0, 1, 2, 3, 20, 13, 6, 7, 0, 0, 0, 0]
 # (shape index, relu, affine) -> seed, where a variant's decisions need another seed than the shape's
 VARIANT_SEEDS = {(4, False, True): 42}
 MARGIN = 1e-6
@@ -151,6 +156,7 @@ def test_torch_ops_float64_match_autograd(i, relu, affine):
 
 # (shape index, relu, affine): the variants tests/test_groupnorm_gpu.py runs beside relu = affine = True
 VARIANTS = [(i, relu, affine) for i in (0, 1, 4) for relu, affine in ((False, True), (True, False), (False, False))]
+VARIANTS += [(8, True, False), (8, False, True)]        # the re-read form under pooling: no affine, no ReLU
 
 
 @pytest.mark.parametrize("i,relu,affine", [(i, True, True) for i in range(len(SHAPES))] + VARIANTS)

@@ -4,7 +4,10 @@ Tolerances.  rtol = atol = 1e-4 is the project's bound for FusedConv2d against t
 and a two-pass fp32 formula are within 5e-7 of float64 (relative to the tensor's maximum) on
 these shapes.  The large-mean bound of 1e-3 (max |a - ref| / max |ref|) lies between what a
 two-pass fp32 variance gives on x = 1000 + randn (at most 2.9e-4, worst on dweight, over 3
-seeds on the CPU) and what the one-pass E[x^2] - mean^2 form gives (at least 2.6e-2 on y)."""
+seeds on the CPU) and what the one-pass E[x^2] - mean^2 form gives (at least 2.6e-2 on y).
+
+SHAPES[8:] exist for the launch geometry: the re-read form under pooling and at odd span phases, both sides
+of the LDS bound (n + 3 <= 16000 floats), and a wave's second channel in pass A; keep them in any edit of the table."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -13,7 +16,8 @@ from torch import nn
 from splitlearning_amd import nn as snn
 from splitlearning_amd.ops import hip_ops, torch_ops
 from splitlearning_amd.optim import FusedAdam
-from test_groupnorm_cpu import EPS, SHAPES, VARIANTS, assert_decision_margins, float_case, make_layer, run_layer
+from test_groupnorm_cpu import (EPS, SHAPES, VARIANTS, assert_decision_margins, float_case, make_layer, run_layer, stats64,
+                                torch_ref)
 from test_optim_cpu import assert_params_close
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +81,83 @@ def test_variants_match_float64(cuda, i, relu, affine):
     _check_close(c, cuda, f"S{i + 1} relu={relu} affine={affine}")
 
 
+# ---------------------------------------------------------------- 2a. the LDS bound
+def test_lds_bound_forms_agree(cuda):
+    """Both sides of the bound between the two span forms, each against its own float64 reference
+    (mean and rstd included): the same x, one float per channel shorter, moves from one to the other."""
+    # csrc/groupnorm.h: kGroupNormLdsFloats = 16000, and a span of n floats stays in LDS while n + 3 <= 16000.
+    # If that constant changes, these shapes no longer straddle the bound: change them (and S10, S11) with it.
+    lds_floats = 16000
+    B, C, G = 2, 4, 2
+    cpg = C // G
+    L = (lds_floats - 3) // cpg + 1                       # 7999: n = 15998 is re-read, L - 1 gives n = 15996 in LDS
+    assert cpg * (L - 1) + 3 <= lds_floats < cpg * L + 3
+    assert SHAPES[10] == (B, C, G, (L,), None)
+    above = float_case(10)
+    cut = lambda t: t[..., :L - 1].contiguous()
+    x, g = cut(above["x"]), cut(above["g"])
+    y, dx, dw, db = torch_ref(x.double(), above["w"].double(), above["b"].double(), g.double(), G, True, None)
+    mean, rstd = stats64(x, G)
+    below = dict(above, x=x, g=g, y=y, dx=dx, dw=dw, db=db, mean=mean, rstd=rstd)
+    for label, c in ((f"n = {cpg * L}, re-read", above), (f"n = {cpg * (L - 1)}, in LDS", below)):
+        assert c["x"].shape == (B, C, c["x"].shape[2]) and c["x"].is_contiguous()
+        assert_decision_margins(c, label)
+        _check_close(c, cuda, label)
+
+
+# ---------------------------------------------------------------- 2b. misaligned base pointers
+def _at_offset(t, off, dev):
+    """A contiguous device copy of t that starts `off` elements into a larger, 16-byte aligned buffer."""
+    buf = torch.empty(t.numel() + 4, device=dev, dtype=t.dtype)
+    assert buf.data_ptr() % 16 == 0
+    v = buf[off:off + t.numel()].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+@pytest.mark.parametrize("i", [0, 11])
+def test_misaligned_base_pointers(cuda, i):
+    """x one float and dy three floats into their storage (hip_ops hands such contiguous views to the
+    kernels as they are: no copy), against float64 at the tolerance of the other tests.
+
+    Not bitwise against the run on ordinarily allocated copies: gn_sweep's split into head, float4s
+    and tail follows the pointer's phase, so which elements a thread adds up, and with that the
+    rounding of every sum, follows it too.  Seen on an MI355X: y, mean, dx, dw and db differ from the
+    aligned run by at most 4.8e-7 (dw and db of S1, one unit in the last place), rstd and am not at
+    all; the offset run is within 1.4e-6 of float64.  The difference from the aligned run is printed."""
+    c = float_case(i)
+    assert_decision_margins(c, f"S{i + 1}")
+    G, pool = c["groups"], c["pool"]
+    w, b = c["w"].to(cuda), c["b"].to(cuda)
+
+    def run(x, dy):
+        y, mean, rstd, am = hip_ops.group_norm_fwd(x, w, b, G, EPS, True, pool)
+        dx, dw, db = hip_ops.group_norm_bwd(dy, x, mean, rstd, w, b, am, G, True, pool, True)
+        return dict(y=y, am=am, mean=mean, rstd=rstd, dx=dx, dw=dw, db=db)
+
+    x1, dy3 = _at_offset(c["x"], 1, cuda), _at_offset(c["g"], 3, cuda)
+    assert x1.data_ptr() % 16 == 4 and dy3.data_ptr() % 16 == 12
+    assert x1.is_contiguous() and dy3.is_contiguous()
+    x0, dy0 = c["x"].to(cuda), c["g"].to(cuda)
+    assert x0.data_ptr() % 16 == 0 and dy0.data_ptr() % 16 == 0
+    ref, got = run(x0, dy0), run(x1, dy3)
+    assert (got["am"] is None) == (pool is None)
+    bad = []
+    for name in ("y", "am", "mean", "rstd", "dx", "dw", "db"):
+        if got[name] is None:
+            continue
+        a, r = got[name].cpu(), ref[name].cpu()
+        assert a.shape == r.shape and a.dtype == r.dtype, name
+        if name == "am":
+            assert torch.equal(a, r) and torch.equal(a, torch_ops.group_norm_fwd(c["x"], c["w"], c["b"], G, EPS, True, pool)[3])
+            continue
+        print(f"S{i + 1} {name}: max |offset - aligned| {(a - r).abs().max().item():.3e}, "
+              f"max |offset - fp64| {(a.double() - c[name]).abs().max().item():.3e}")
+        if not torch.allclose(a.double(), c[name], rtol=1e-4, atol=1e-4):
+            bad.append(name)
+    assert not bad, f"beyond rtol = atol = 1e-4 of float64: {bad}"
+
+
 # ---------------------------------------------------------------- 3. large mean
 @pytest.mark.parametrize("i", [0, 1, 2, 3])
 def test_large_mean_input(cuda, i):
@@ -89,7 +170,7 @@ def test_large_mean_input(cuda, i):
 
 
 # ---------------------------------------------------------------- 4. argmax and ties
-@pytest.mark.parametrize("i", [1, 4])
+@pytest.mark.parametrize("i", [1, 4, 8, 11])
 def test_argmax_positions_match_torch_ops(cuda, i):
     c = float_case(i)
     assert_decision_margins(c, f"S{i + 1}")
