@@ -21,6 +21,7 @@
 #include "optim.h"
 #include "conv2d.h"
 #include "groupnorm.h"
+#include "cutcodec.h"
 
 namespace sl {
 hipError_t conv_fwd(const void* x, bool x_u8, const int64_t* idx, int64_t row0, int B, const float* w,
@@ -845,6 +846,62 @@ void group_norm_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor&
         "group_norm_bwd");
 }
 
+// ---------------------------------------------------------------- cut codec (cutcodec.hip)
+// x / y [R, K] fp32, payload int8 [R, K] (8 bits) or uint8 [R, ceil(K / 2)] (4 bits), scales fp32
+// [R, ceil(K / group)]: contiguous, on the current device.  R, K < 2^31; the kernels index in 64 bits.
+void cut_need(const at::Tensor& t, at::ScalarType ty, const char* name, const char* tyname) {
+  need_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == ty, name, " must be ", tyname);
+  TORCH_CHECK(t.dim() == 2 && t.is_contiguous(), name, " must be 2-D and contiguous");
+  TORCH_CHECK(t.get_device() == c10::hip::current_device(), name, " must be on the current device");
+}
+
+sl::CutShape cut_shape(int64_t R, int64_t K, int64_t bits, int64_t group, uint64_t seed, bool stochastic) {
+  TORCH_CHECK(bits == 8 || bits == 4, "cut codec: bits must be 8 or 4");
+  TORCH_CHECK(group == 16 || group == 32 || group == 64 || group == 128 || group == 256,
+              "cut codec: group must be 16, 32, 64, 128 or 256");
+  TORCH_CHECK(R >= 1 && K >= 1, "cut codec: empty input");
+  TORCH_CHECK(R < (int64_t(1) << 31) && K < (int64_t(1) << 31), "cut codec: R and K must be below 2^31");
+  sl::CutShape s{};
+  s.R = (int)R, s.K = (int)K, s.group = (int)group, s.ng = (int)((K + group - 1) / group), s.bits = (int)bits;
+  s.stochastic = stochastic, s.seed_lo = (uint32_t)seed, s.seed_hi = (uint32_t)(seed >> 32);
+  return s;
+}
+
+void cut_check_wire(const at::Tensor& payload, const at::Tensor& scales, const sl::CutShape& s) {
+  if (s.bits == 8) cut_need(payload, at::kChar, "payload", "int8");
+  else cut_need(payload, at::kByte, "payload", "uint8");
+  cut_need(scales, at::kFloat, "scales", "float32");
+  const int64_t kb = s.bits == 8 ? s.K : ((int64_t)s.K + 1) / 2;
+  TORCH_CHECK(payload.size(0) == s.R && payload.size(1) == kb, "payload must be [R, K] (8 bits) or [R, ceil(K / 2)] (4 bits)");
+  TORCH_CHECK(scales.size(0) == s.R && scales.size(1) == s.ng, "scales must be [R, ceil(K / group)]");
+}
+
+void cut_pack(const at::Tensor& x, at::Tensor& payload, at::Tensor& scales, int64_t bits, int64_t group, uint64_t seed,
+              bool stochastic) {
+  cut_need(x, at::kFloat, "x", "float32");
+  const sl::CutShape s = cut_shape(x.size(0), x.size(1), bits, group, seed, stochastic);
+  cut_check_wire(payload, scales, s);
+  TORCH_CHECK(payload.device() == x.device() && scales.device() == x.device(), "cut_pack: tensors on different devices");
+  check(sl::cut_pack(x.data_ptr<float>(), payload.data_ptr(), scales.data_ptr<float>(), s, cur_stream()), "cut_pack");
+}
+
+void cut_unpack(const at::Tensor& payload, const at::Tensor& scales, at::Tensor& y, int64_t bits, int64_t group) {
+  cut_need(y, at::kFloat, "y", "float32");
+  const sl::CutShape s = cut_shape(y.size(0), y.size(1), bits, group, 0, false);
+  cut_check_wire(payload, scales, s);
+  TORCH_CHECK(payload.device() == y.device() && scales.device() == y.device(), "cut_unpack: tensors on different devices");
+  check(sl::cut_unpack(payload.data_ptr(), scales.data_ptr<float>(), y.data_ptr<float>(), s, cur_stream()), "cut_unpack");
+}
+
+void cut_roundtrip(const at::Tensor& x, at::Tensor& y, int64_t bits, int64_t group, uint64_t seed, bool stochastic) {
+  cut_need(x, at::kFloat, "x", "float32");
+  cut_need(y, at::kFloat, "y", "float32");
+  TORCH_CHECK(y.sizes() == x.sizes() && y.device() == x.device(), "cut_roundtrip: y must have x's shape and device");
+  const sl::CutShape s = cut_shape(x.size(0), x.size(1), bits, group, seed, stochastic);
+  check(sl::cut_roundtrip(x.data_ptr<float>(), y.data_ptr<float>(), s, cur_stream()), "cut_roundtrip");
+}
+
 // ---------------------------------------------------------------- loss / metrics
 void softmax_ce(const at::Tensor& x, const at::Tensor& y, int64_t ignore, double scale, at::Tensor& loss_rows,
                 const OptT& d) {
@@ -1043,6 +1100,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv3x3_wgrad_ws", &conv3x3_wgrad_ws);
   m.def("group_norm_fwd", &group_norm_fwd);
   m.def("group_norm_bwd", &group_norm_bwd);
+  m.def("cut_pack", &cut_pack);
+  m.def("cut_unpack", &cut_unpack);
+  m.def("cut_roundtrip", &cut_roundtrip);
   m.attr("multi_opt_chunk") = (int64_t)sl::kMultiOptChunk;
   m.attr("multi_opt_max") = (int64_t)sl::kMultiOptMax;
   m.def("softmax_ce", &softmax_ce);

@@ -24,6 +24,12 @@ __device__ __forceinline__ bool sl_hash_keep(uint32_t seed_lo, uint32_t seed_hi,
   uint32_t h = sl_fmix32(a ^ ((col * 0x85EBCA77u) ^ seed_hi));
   return h >= thresh;
 }
+// The hash sl_hash_keep thresholds (ops/rng.py hash32): the cut codec's stochastic rounding
+// takes its uniform from the top 24 bits.
+__device__ __forceinline__ uint32_t sl_hash32(uint32_t seed_lo, uint32_t seed_hi, uint32_t row, uint32_t col) {
+  uint32_t a = sl_fmix32((row * 0x9E3779B1u) ^ seed_lo);
+  return sl_fmix32(a ^ ((col * 0x85EBCA77u) ^ seed_hi));
+}
 
 // ------------------------------------------------------------------ bf16 compute
 // `--dtype bf16`: a GEMM operand rounded to bf16 (RNE; v_cvt_pk_bf16_f32) and back.  The
@@ -88,6 +94,17 @@ __device__ __forceinline__ float sl_group_sum(float v) {
   if (SUB >= 16) v += sl_dpp<0x140>(v);
   if (SUB >= 32) v += __shfl_xor(v, 16, 64);
   if (SUB >= 64) v += __shfl_xor(v, 32, 64);
+  return v;
+}
+// The same for the maximum (order-independent, so every lane's result is bitwise the group's).
+template <int SUB>
+__device__ __forceinline__ float sl_group_max(float v) {
+  if (SUB >= 2) v = fmaxf(v, sl_dpp<0xB1>(v));
+  if (SUB >= 4) v = fmaxf(v, sl_dpp<0x4E>(v));
+  if (SUB >= 8) v = fmaxf(v, sl_dpp<0x141>(v));
+  if (SUB >= 16) v = fmaxf(v, sl_dpp<0x140>(v));
+  if (SUB >= 32) v = fmaxf(v, __shfl_xor(v, 16, 64));
+  if (SUB >= 64) v = fmaxf(v, __shfl_xor(v, 32, 64));
   return v;
 }
 

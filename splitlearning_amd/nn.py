@@ -22,6 +22,10 @@ gradient-norm clipping), and any `torch.optim` optimizer works too:
   ReLU and pool two kernels per direction with no un-pooled activation stored.  It keeps no
   buffers, so weight relay, snapshots and unlearning carry a model that uses it as they are.
 * `softmax_cross_entropy`: mean CrossEntropyLoss as one fused forward+backward kernel.
+* `CutCodec`: the cut itself.  What crosses it is block-quantised to int8 or int4 with one fp32
+  scale per group of a row: the activation to the nearest step, its gradient with stochastic
+  (unbiased) rounding, one streaming kernel each.  `cut_pack` / `cut_unpack` produce and read the
+  wire tensors (`CutPacket`) for a transport.  No parameters and no buffers.
 
 On CPU tensors the same layers run the eager torch implementations (ops/torch_ops.py),
 so a model is written once. State-dict keys match `nn.Linear` / `nn.Conv2d` / `nn.GroupNorm` /
@@ -30,6 +34,7 @@ so a model is written once. State-dict keys match `nn.Linear` / `nn.Conv2d` / `n
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 
 import torch
 from torch import nn
@@ -306,4 +311,111 @@ def softmax_cross_entropy(logits, labels, ignore_index: int = -100):
     return _SoftmaxCEFn.apply(logits, labels, ignore_index)
 
 
-__all__ = ["FusedLinear", "FusedConv2d", "FusedGroupNorm", "FusedConvFront", "softmax_cross_entropy"]
+# ------------------------------------------------------------------ the cut
+_CUT_BITS = (None, 4, 8)
+
+
+def _cut_args(name, bits, group, what="bits"):
+    if bits not in _CUT_BITS or isinstance(bits, bool):
+        raise ValueError(f"{name}: {what} must be None, 4 or 8, got {bits!r}")
+    if group not in ops.torch_ops.CUT_GROUPS:
+        raise ValueError(f"{name}: group must be one of {ops.torch_ops.CUT_GROUPS}, got {group!r}")
+
+
+def _cut_input(name, x):
+    if x.dim() < 2:
+        raise ValueError(f"{name}: expected [B, *] with at least 2 dimensions, got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name}: input must be float32, got {x.dtype}")
+
+
+class _CutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bits, grad_bits, group: int, seed: int):
+        ctx.grad_bits, ctx.group, ctx.seed = grad_bits, group, seed
+        if bits is None:
+            return x.view_as(x)
+        y = ops.impl(x.device).cut_roundtrip(x.reshape(x.shape[0], -1), bits, group)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.grad_bits is None:
+            return dy, None, None, None, None
+        dx = ops.impl(dy.device).cut_roundtrip(dy.reshape(dy.shape[0], -1), ctx.grad_bits, ctx.group, ctx.seed)
+        return dx.view(dy.shape), None, None, None, None
+
+
+class CutCodec(nn.Module):
+    """The cut of a split model: what the other side receives after int8 / int4 block quantisation.
+
+    x [B, *] float32 is read as [B, K]; each row is cut into groups of `group` (16, 32, 64, 128 or
+    256) consecutive elements, the last of a row possibly short, and a group is sent as integers in
+    [-qmax, qmax] (qmax = 127 at 8 bits, 7 at 4) with one fp32 scale = max |x| / qmax.  At
+    group = 64 that is 1.0625 bytes per element at 8 bits and 0.5625 at 4, against 4.
+
+    Forward: y = the dequantised activation, rounded to the nearest step (half to even); the same
+    in `train()` and `eval()`, since the wire is there at inference too.  Backward: dx = the
+    gradient quantised to `grad_bits` with stochastic rounding, which is unbiased; its seed is
+    `step_seed(seed, 0, calls)`, `calls` counting forward calls.  `grad_bits=None` passes the
+    gradient through, `bits=None` the activation.  No parameters and no buffers, so state dicts,
+    weight relay, snapshots and unlearning carry a model that contains it unchanged."""
+
+    def __init__(self, bits=8, grad_bits=8, group: int = 64, seed: int = 0):
+        super().__init__()
+        _cut_args("CutCodec", bits, group)
+        _cut_args("CutCodec", grad_bits, group, "grad_bits")
+        self.bits, self.grad_bits, self.group, self.seed = bits, grad_bits, group, seed
+        self.calls = 0
+
+    def forward(self, x):
+        _cut_input("CutCodec", x)
+        self.calls += 1
+        if self.bits is None and self.grad_bits is None:
+            return x
+        return _CutFn.apply(x, self.bits, self.grad_bits, self.group, step_seed(self.seed, 0, self.calls))
+
+    def extra_repr(self):
+        return f"bits={self.bits}, grad_bits={self.grad_bits}, group={self.group}"
+
+
+@dataclass
+class CutPacket:
+    """What `cut_pack` makes and a transport ships: `payload` (int8 [R, K] at 8 bits; uint8
+    [R, ceil(K / 2)] at 4 bits, the even column in the low nibble) and `scales` (fp32
+    [R, ceil(K / group)]), with the `shape` of the tensor they came from."""
+    payload: torch.Tensor
+    scales: torch.Tensor
+    shape: tuple
+    bits: int
+    group: int
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors())
+
+    def tensors(self):
+        return self.payload, self.scales
+
+
+def cut_pack(x, bits: int = 8, group: int = 64, seed=None) -> CutPacket:
+    """Quantise x [B, *] float32 for the wire: nearest rounding, or stochastic with a 64-bit
+    `seed`.  Not differentiable (the result is integers): inside a model use `CutCodec`."""
+    _cut_args("cut_pack", bits, group)
+    if bits is None:
+        raise ValueError("cut_pack: bits must be 4 or 8, got None")
+    _cut_input("cut_pack", x)
+    x = x.detach()
+    payload, scales = ops.impl(x.device).cut_pack(x.reshape(x.shape[0], -1), bits, group, seed)
+    return CutPacket(payload, scales, tuple(x.shape), bits, group)
+
+
+def cut_unpack(packet: CutPacket) -> torch.Tensor:
+    """The float32 tensor of `packet.shape` the packet stands for."""
+    K = math.prod(packet.shape[1:])
+    y = ops.impl(packet.payload.device).cut_unpack(packet.payload, packet.scales, K, packet.bits, packet.group)
+    return y.view(packet.shape)
+
+
+__all__ = ["FusedLinear", "FusedConv2d", "FusedGroupNorm", "FusedConvFront", "softmax_cross_entropy", "CutCodec",
+           "CutPacket", "cut_pack", "cut_unpack"]

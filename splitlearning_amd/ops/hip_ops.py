@@ -252,6 +252,39 @@ def group_norm_bwd(dy, x, mean, rstd, weight, bias, am, groups: int, relu: bool,
     return dx, dw, db
 
 
+# ---------------------------------------------------------------- cut codec
+# csrc/cutcodec.hip: int8 / int4 block quantisation of the tensor that crosses the cut, one kernel
+# per call, bitwise equal to ops/torch_ops.py (the format's definition).  A contiguous view that
+# starts anywhere in its storage goes to the kernels as it is.
+def _cut_wire(x2d, bits: int, group: int):
+    R, K = x2d.shape
+    payload = torch.empty((R, K) if bits == 8 else (R, (K + 1) // 2), device=x2d.device,
+                          dtype=torch.int8 if bits == 8 else torch.uint8)
+    return payload, torch.empty(R, -(-K // group), device=x2d.device, dtype=torch.float32)
+
+
+def cut_pack(x2d, bits: int, group: int, seed=None):
+    """(payload, scales); nearest (half to even) without a seed, stochastic with one."""
+    x2d = x2d.contiguous()
+    payload, scales = _cut_wire(x2d, bits, group)
+    C().cut_pack(x2d, payload, scales, int(bits), int(group), (seed or 0) & M64, seed is not None)
+    return payload, scales
+
+
+def cut_unpack(payload, scales, K: int, bits: int, group: int):
+    y = torch.empty(payload.shape[0], K, device=payload.device, dtype=torch.float32)
+    C().cut_unpack(payload.contiguous(), scales.contiguous(), y, int(bits), int(group))
+    return y
+
+
+def cut_roundtrip(x2d, bits: int, group: int, seed=None):
+    """cut_unpack(*cut_pack(...)) in one pass: x is read once and x^ written once."""
+    x2d = x2d.contiguous()
+    y = torch.empty_like(x2d)
+    C().cut_roundtrip(x2d, y, int(bits), int(group), (seed or 0) & M64, seed is not None)
+    return y
+
+
 # ---------------------------------------------------------------- linear
 # training batches (M <= 128) run the skinny split-K kernels.  Many rows (evaluation over a
 # test set, large batches): the forward product runs the in-tree LDS-tiled MFMA GEMM

@@ -44,6 +44,17 @@ def keep_mask(seed: int, rows: int, cols: int, p: float, col_offset: int = 0,
     return h >= thresh
 
 
+def hash32(seed: int, rows: int, cols: int, device=None) -> torch.Tensor:
+    """The 32-bit hash of (seed, row, column) that `keep_mask` thresholds, as int64 [rows, cols]
+    (`sl_hash32` in `csrc/common.h`).  The cut codec's stochastic rounding draws its uniform
+    from the top 24 bits: u = (h >> 8) * 2^-24."""
+    lo, hi = split_seed(seed)
+    r = torch.arange(rows, dtype=torch.int64, device=device).view(-1, 1)
+    c = torch.arange(cols, dtype=torch.int64, device=device).view(1, -1)
+    a = _fmix32(((r * C_ROW) & M32) ^ lo)
+    return _fmix32(a ^ (((c * C_COL) & M32) ^ hi))
+
+
 def step_seed(base: int, layer: int, step: int) -> int:
     """Derive the per-(layer, step) 64-bit seed on the host (no device state)."""
     x = (base * 0x9E3779B97F4A7C15 + layer * 0xBF58476D1CE4E5B9 + step * 0x94D049BB133111EB)

@@ -12,7 +12,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from .rng import keep_mask
+from .rng import hash32, keep_mask
 
 CUT = 5408
 
@@ -152,6 +152,76 @@ def group_norm_bwd(dy, x, mean, rstd, weight, bias, am, groups: int, relu: bool,
         m1, m2 = wg.mean(dim=2, keepdim=True), (wg * xg).mean(dim=2, keepdim=True)
         dx = (rstd.unsqueeze(-1) * (wg - m1 - xg * m2)).reshape(x.shape)
     return dx, dweight, dbias
+
+
+# ---------------------------------------------------------------- cut codec
+# The definition of the cut-layer format (csrc/cutcodec.hip matches it bit for bit).  x2d [R, K]
+# fp32 is cut into ng = ceil(K / group) groups of `group` consecutive elements of a row (the last
+# may be short).  Per group, in fp32: absmax = max |x|, scale = absmax / qmax, inv = qmax / absmax
+# (0 for a zero group), q = clamp(rint(x * inv)) or, with a seed, clamp(floor((x * inv) + u)) with
+# u = (hash32(seed, row, column) >> 8) * 2^-24; x^ = float(q) * scale.  Every step is its own torch
+# op, so nothing is contracted into an FMA, and the divisions are tensor / tensor (a GPU division
+# by a Python scalar multiplies by its reciprocal, which rounds differently).
+CUT_GROUPS = (16, 32, 64, 128, 256)
+CUT_QMAX = {8: 127.0, 4: 7.0}
+
+
+def _cut_check(t, bits, group):
+    if bits not in CUT_QMAX:
+        raise ValueError(f"cut codec: bits must be 8 or 4, got {bits!r}")
+    if group not in CUT_GROUPS:
+        raise ValueError(f"cut codec: group must be one of {CUT_GROUPS}, got {group!r}")
+    if t.dim() != 2:
+        raise ValueError(f"cut codec: expected a 2-D tensor, got {tuple(t.shape)}")
+
+
+def _cut_per_element(scales, K: int, group: int):
+    """[R, ng] -> [R, K]: each group's value at its elements."""
+    return scales.repeat_interleave(group, dim=1)[:, :K]
+
+
+def cut_pack(x2d, bits: int, group: int, seed=None):
+    """(payload, scales): payload int8 [R, K] at 8 bits; uint8 [R, ceil(K / 2)] at 4 bits, column
+    2j in the low nibble of byte j and 2j + 1 in the high one (two's complement, 0 past an odd K);
+    scales fp32 [R, ng].  Nearest (half to even) without a seed, stochastic with one."""
+    _cut_check(x2d, bits, group)
+    if x2d.dtype != torch.float32:
+        raise ValueError(f"cut codec: input must be float32, got {x2d.dtype}")
+    R, K = x2d.shape
+    ng = -(-K // group)
+    absmax = F.pad(x2d.abs(), (0, ng * group - K)).view(R, ng, group).amax(dim=2)
+    qmax = torch.full_like(absmax, CUT_QMAX[bits])
+    scales = absmax / qmax
+    inv = torch.where(absmax > 0, qmax / absmax, torch.zeros_like(absmax))
+    t = x2d * _cut_per_element(inv, K, group)
+    if seed is None:
+        q = torch.round(t)
+    else:
+        u = (hash32(seed, R, K, x2d.device) >> 8).to(torch.float32) * 2.0 ** -24
+        q = torch.floor(t + u)
+    q = q.clamp(-CUT_QMAX[bits], CUT_QMAX[bits])
+    if bits == 8:
+        return q.to(torch.int8), scales
+    nib = F.pad(q.to(torch.int32) & 0xF, (0, K % 2))
+    return (nib[:, 0::2] | (nib[:, 1::2] << 4)).to(torch.uint8), scales
+
+
+def cut_unpack(payload, scales, K: int, bits: int, group: int):
+    """x^ [R, K] fp32 = float(q) * scale of its group."""
+    _cut_check(payload, bits, group)
+    if bits == 8:
+        q = payload.to(torch.float32)
+    else:
+        p = payload.to(torch.int32)
+        nib = torch.stack((p & 0xF, p >> 4), dim=2).view(p.shape[0], -1)[:, :K]
+        q = ((nib ^ 8) - 8).to(torch.float32)
+    return q * _cut_per_element(scales, K, group)
+
+
+def cut_roundtrip(x2d, bits: int, group: int, seed=None):
+    """cut_unpack(*cut_pack(x2d, ...)): what the other side of the cut receives."""
+    payload, scales = cut_pack(x2d, bits, group, seed)
+    return cut_unpack(payload, scales, x2d.shape[1], bits, group)
 
 
 # ---------------------------------------------------------------- linear
