@@ -85,6 +85,16 @@ softmax_ce_wide_kernel(const float* __restrict__ x, int ldx, const int64_t* __re
   }
 }
 
+// torch.argmax's order, the prediction's definition (ops/torch_ops.py eval_counters): does
+// (v, c) come before (best, arg)?  A NaN is the maximum, larger values next, and among equals
+// (two NaNs included) the lower column.  The start value (-inf, 0x7fffffff) loses to every
+// real column, a -inf one too, so a row of nothing but -inf predicts column 0.
+__device__ __forceinline__ bool sl_argmax_before(float v, int c, float best, int arg) {
+  const bool vn = v != v, bn = best != best;
+  if (vn || bn) return vn && (!bn || c < arg);
+  return v > best || (v == best && c < arg);
+}
+
 // counters[6] += {correct, total, correct_unlearned, total_unlearned, correct_remaining, total_remaining}
 __global__ void __launch_bounds__(256)
 eval_counters_kernel(const float* __restrict__ x, int ldx, const int64_t* __restrict__ y, int64_t omit,
@@ -100,13 +110,13 @@ eval_counters_kernel(const float* __restrict__ x, int ldx, const int64_t* __rest
     int arg = 0x7fffffff;
     for (int c = lane; c < C; c += 64) {
       const float v = xr[c];
-      if (v > best) { best = v; arg = c; }
+      if (sl_argmax_before(v, c, best, arg)) { best = v; arg = c; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ob = __shfl_xor(best, o, 64);
       const int oa = __shfl_xor(arg, o, 64);
-      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+      if (sl_argmax_before(ob, oa, best, arg)) { best = ob; arg = oa; }
     }
     if (lane == 0) {
       const int64_t lab = y[row];
@@ -160,7 +170,9 @@ hipError_t eval_counters(const float* x, int ldx, const int64_t* y, int64_t omit
 // the whole layer in ONE workgroup (the separate path is four launches of a few us each
 // for 1,010 parameters).  dX uses the weights before the update; with mask_dx it is also
 // masked by [X > 0], the ReLU backward of the layer that produced X (Bob's model2 ends in a
-// ReLU whose output X is), so the producer skips its own mask launch.  M*K, C*K <= 4096.
+// ReLU whose output X is), so the producer skips its own mask launch.  M*K, C*K <= 4096 and
+// M*C <= 1024 (the LDS arrays); within those M and C may each exceed the 256 threads, so every
+// per-row and per-class stage strides over the workgroup.
 __global__ void __launch_bounds__(256)
 head_step_kernel(const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
                  const int64_t* __restrict__ y, int64_t ignore, float scale, float* __restrict__ loss_rows,
@@ -201,12 +213,12 @@ head_step_kernel(const float* __restrict__ X, const float* __restrict__ W, const
     sd[i] = v + (bias ? bias[c] : 0.f);
   }
   __syncthreads();
-  // softmax-CE per row
-  if (tid < M) {
-    float* r = sd + tid * C;
-    const int64_t lab = y[tid];
+  // softmax-CE per row (M may exceed the workgroup: M * C <= 1024 admits up to 1024 rows)
+  for (int m = tid; m < M; m += 256) {
+    float* r = sd + m * C;
+    const int64_t lab = y[m];
     if (lab == ignore) {
-      loss_rows[tid] = 0.f;
+      loss_rows[m] = 0.f;
       for (int c = 0; c < C; ++c) r[c] = 0.f;
     } else {
       float mx = -INFINITY;
@@ -214,7 +226,7 @@ head_step_kernel(const float* __restrict__ X, const float* __restrict__ W, const
       float se = 0.f;
       for (int c = 0; c < C; ++c) se += expf(r[c] - mx);
       const float inv = 1.f / se;
-      loss_rows[tid] = mx + logf(se) - r[lab];
+      loss_rows[m] = mx + logf(se) - r[lab];
       for (int c = 0; c < C; ++c) {
         float p = expf(r[c] - mx) * inv;
         if (c == lab) p -= 1.f;
@@ -245,14 +257,19 @@ head_step_kernel(const float* __restrict__ X, const float* __restrict__ W, const
   for (int j = 0; j < PF; ++j)       // compile-time register index (no scratch)
     if (tid + 256 * j < C * K) wstep(tid + 256 * j, r0[j], r1[j]);
   for (int i = tid + 256 * PF; i < C * K; i += 256) wstep(i, s0w[i], s1w ? s1w[i] : 0.f);
-  if (bias && tid < C) {
-    float g = 0.f;
-    for (int m = 0; m < M; ++m) g += sd[m * C + tid];
-    float pp = rbp, a0 = rb0, a1 = rb1;
-    sl_opt_update(o, pp, g, a0, a1);
-    if (o.kind != 0) bout[tid] = pp;
-    s0b[tid] = a0;
-    if (s1b) s1b[tid] = a1;
+  if (bias) {
+    // C may exceed the workgroup too (C * K <= 4096): class tid from the registers loaded at
+    // the start, classes tid + 256, .. from memory
+    for (int c = tid; c < C; c += 256) {
+      const bool first = c == tid;
+      float pp = first ? rbp : bias[c], a0 = first ? rb0 : s0b[c], a1 = first ? rb1 : (s1b ? s1b[c] : 0.f);
+      float g = 0.f;
+      for (int m = 0; m < M; ++m) g += sd[m * C + c];
+      sl_opt_update(o, pp, g, a0, a1);
+      if (o.kind != 0) bout[c] = pp;
+      s0b[c] = a0;
+      if (s1b) s1b[c] = a1;
+    }
   }
 }
 
@@ -399,6 +416,10 @@ hipError_t head_step(const float* X, float* W, float* b, const int64_t* y, int64
                      SlOpt o, bool mask_dx, hipStream_t st) {
   if (M <= 0) return hipSuccess;
   if (M * K > 4096 || C * K > 4096 || M * C > 1024) return hipErrorInvalidValue;
+  // `(K & 3) == 0` and `al` guard the MFMA kernel's float4 loads for native callers of this
+  // function (csrc/split.cpp).  Through the Python binding they are always true: its need_rows
+  // check rejects X or W whose rows are not 16-byte aligned (K % 4 != 0 included) before this
+  // runs, so the FMA kernel below does not serve unaligned heads from Python.
   const bool al = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W)) & 15) == 0;
   if (M <= 16 && C <= 16 && K <= 128 && (K & 3) == 0 && C * K <= 2048 && al) {
     if (g_bf16)
