@@ -1,9 +1,10 @@
 // Python bindings for the gfx950 kernels (pybind11 module `splitlearning_amd._C`).
 //
-// Thin by design: validate shapes/dtypes/devices on the host (a kernel must never
-// see an operand its grid does not assume), fetch the current HIP stream from the
-// PyTorch-ROCm stream registry, and call the launcher.  All buffers are
-// caller-allocated so the same calls can be captured into a HIP graph.
+// Each binding validates its operands on the host (a kernel must never see an operand its
+// grid does not assume) with the shared checks of args.h, fetches the current HIP stream from
+// the PyTorch-ROCm stream registry and calls the launcher (kernels.h and the per-family
+// headers).  All buffers are caller-allocated so the same calls can be captured into a HIP
+// graph.  The executors and the hand-off stress entry register themselves (sl_register_*).
 //
 // Optimizer hyper-parameters travel as (kind, lr, beta1, beta2, eps, wd, momentum, t, dyn):
 // kind 0 = write the gradient into s0, 1 = SGD(momentum), 2 = Adam (L2 weight decay);
@@ -11,88 +12,19 @@
 // (graph replay).  Dropout seeds likewise: (seed, dseed) with dseed = device address
 // of {seed_lo, seed_hi} or 0.
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
 
+#include "args.h"
 #include "common.h"
-#include "fused.h"
-#include "handoff.h"
-#include "host.h"
-#include "optim.h"
 #include "conv2d.h"
-#include "groupnorm.h"
 #include "cutcodec.h"
-
-namespace sl {
-hipError_t conv_fwd(const void* x, bool x_u8, const int64_t* idx, int64_t row0, int B, const float* w,
-                    const float* b, float* y, uint8_t* am, hipStream_t st, const int64_t* lab_in,
-                    int64_t* lab_out, const ConvPending* pend);
-hipError_t conv_local_step(const void* x, bool x_u8, const int64_t* idx, const int64_t* labels, int B, float* w,
-                           float* b, float* slab, float* loss_rows, float* s0w, float* s1w, float* s0b, float* s1b,
-                           SlOpt o, hipStream_t st);
-hipError_t conv_local_epoch(const void* x, bool x_u8, const int64_t* order, int64_t n, int B, const int64_t* labels,
-                            float* w, float* b, float* s0w, float* s1w, float* s0b, float* s1b, float* ws,
-                            int64_t ws_elems, float* loss_rows, SlOpt (*opt)(void*, int64_t), void* optctx,
-                            int64_t t0, hipStream_t st);
-hipError_t conv_bwd_step(const float* dy, const float* y, const uint8_t* am, const void* x, bool x_u8,
-                         const int64_t* idx, int B, float* w, float* b, float* slab, float* s0w, float* s1w,
-                         float* s0b, float* s1b, SlOpt o, hipStream_t st, bool defer, const ConvPending* pend);
-hipError_t conv_local_epoch_multi(const MultiAlice* al, int k, int B, SlOpt (*opt)(void*, int64_t), void* optctx,
-                                  void* table, int64_t table_bytes, hipStream_t st);
-size_t alice_step_desc_bytes();
-hipError_t conv_apply(const ConvPending& p, float* w, float* b, hipStream_t st);
-hipError_t conv_fwd_multi(const FrontFwdSet& set, int64_t chunk, hipStream_t st);
-hipError_t head_step(const float* X, float* W, float* b, const int64_t* y, int64_t ignore, float scale,
-                     float* loss_rows, float* dX, float* s0w, float* s1w, float* s0b, float* s1b, int M, int K, int C,
-                     SlOpt o, bool mask_dx, hipStream_t st);
-hipError_t linear_fwd(const float* X, int ldx, const float* W, int ldw, float* Y, int ldy, int M, int N, int K,
-                      Epi e, float* ws, int64_t ws_elems, hipStream_t st);
-hipError_t linear_dgrad(const float* dZ, int ldz, const float* W, int ldw, const float* hprev, int ldh,
-                        float scale, float* dX, int ldx, float* ws, int64_t ws_elems, int M, int N, int K,
-                        hipStream_t st);
-hipError_t linear_epilogue(const float* P, int ldp, float* Y, int ldy, int M, int N, Epi e, int S, int64_t slab,
-                           hipStream_t st);
-hipError_t gemm_nn_dgrad(const float* dZ, int ldz, const float* W, int ldw, const float* hprev, int ldh, float scale,
-                         float* dX, int ldx, int M, int R, int K, float* ws, int64_t ws_elems, hipStream_t st);
-hipError_t linear_fwd_partial(const float* X, int ldx, const float* W, int ldw, int M, int N, int K, float* ws,
-                              int64_t ws_elems, int max_split, int* S_out, hipStream_t st);
-hipError_t linear_wgrad_opt(const float* dZ, int ldz, const float* A, int lda, float* W, int ldw, float* s0,
-                            float* s1, float* bias, float* sb0, float* sb1, int M, int N, int K, SlOpt o,
-                            hipStream_t st);
-hipError_t opt_flat(float* p, const float* g, float* s0, float* s1, int64_t n, SlOpt o, hipStream_t st);
-hipError_t relu_mask(const float* d, const float* h, float scale, float* out, int64_t n, hipStream_t st);
-hipError_t softmax_ce(const float* x, int ldx, const int64_t* y, int64_t ignore, float scale, float* loss_rows,
-                      float* d, int ldd, int M, int C, hipStream_t st);
-hipError_t eval_counters(const float* x, int ldx, const int64_t* y, int64_t omit, unsigned long long* counters,
-                         int M, int C, hipStream_t st);
-}  // namespace sl
+#include "fused.h"
+#include "groupnorm.h"
+#include "kernels.h"
+#include "optim.h"
 
 namespace {
 
-using OptT = c10::optional<at::Tensor>;
-
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
-
-void check(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e)); }
-
-void need_cuda(const at::Tensor& t, const char* name) { TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor"); }
-void need_f32(const at::Tensor& t, const char* name) {
-  need_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
-}
-// row-major 2-D with unit column stride and 16-byte aligned rows (float4 loads)
-void need_rows(const at::Tensor& t, const char* name) {
-  need_f32(t, name);
-  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1, name, " must be 2-D with unit column stride");
-  TORCH_CHECK(t.stride(0) % 4 == 0 && (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) == 0, name,
-              " rows must be 16-byte aligned");
-}
-// 2-D with unit column stride (scalar access only)
-void need_2d(const at::Tensor& t, const char* name) {
-  need_f32(t, name);
-  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1, name, " must be 2-D with unit column stride");
-}
-float* fptr(const OptT& t) { return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr; }
+using namespace sl::args;   // OptT, cur_stream, has, opt_ptr, opt_ws, the need_* checks
 
 SlOpt make_opt(int64_t kind, double lr, double beta1, double beta2, double eps, double wd, double momentum,
                int64_t t, int64_t dyn) {
@@ -101,7 +33,7 @@ SlOpt make_opt(int64_t kind, double lr, double beta1, double beta2, double eps, 
 }
 
 Epi make_epi(const OptT& bias, bool relu, double drop_p, uint64_t seed, int64_t col_off, int64_t dseed) {
-  return sl::make_epi_raw(fptr(bias), relu, drop_p, seed, (int)col_off, reinterpret_cast<const uint32_t*>(dseed));
+  return sl::make_epi_raw(opt_ptr(bias), relu, drop_p, seed, (int)col_off, reinterpret_cast<const uint32_t*>(dseed));
 }
 
 #define OPT_ARGS int64_t kind, double lr, double beta1, double beta2, double eps, double wd, double momentum, \
@@ -128,42 +60,102 @@ void check_slab(const at::Tensor& slab, int64_t B) {
   TORCH_CHECK(slab.is_contiguous() && slab.numel() >= B * 320, "slab workspace [B,320]");
 }
 
+// The operands of the front-conv bindings, checked, as the launchers take them.  A binding
+// names the tensors it has (Has); the others stay null in the result.
+struct FrontState {   // the optimizer state of w and b: first moments / momentum, Adam's second or None
+  const at::Tensor& s0w;
+  const OptT& s1w;
+  const at::Tensor& s0b;
+  const OptT& s1b;
+};
+struct FrontHas {
+  const at::Tensor *idx = nullptr, *y = nullptr, *am = nullptr, *labels = nullptr, *slab = nullptr;
+  const FrontState* state = nullptr;
+  const char* labels_name = "labels";
+};
+struct Front {
+  const void* x = nullptr;
+  bool u8 = false;
+  float *w = nullptr, *b = nullptr, *y = nullptr, *slab = nullptr;
+  float *s0w = nullptr, *s1w = nullptr, *s0b = nullptr, *s1b = nullptr;
+  uint8_t* am = nullptr;
+  const int64_t *idx = nullptr, *labels = nullptr;
+};
+Front front_args(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b, int64_t B, const FrontHas& h) {
+  Front f;
+  check_x(x);
+  check_params(w, b);
+  f.x = x.data_ptr();
+  f.u8 = x.scalar_type() == at::kByte;
+  f.w = w.data_ptr<float>();
+  f.b = b.data_ptr<float>();
+  if (h.idx) {
+    check_idx(*h.idx, B);
+    f.idx = h.idx->data_ptr<int64_t>();
+  }
+  if (h.slab) {
+    check_slab(*h.slab, B);
+    f.slab = h.slab->data_ptr<float>();
+  }
+  if (h.y) {
+    need_f32(*h.y, "y");
+    TORCH_CHECK(h.y->is_contiguous() && h.y->numel() >= B * 5408, "y too small");
+    f.y = h.y->data_ptr<float>();
+  }
+  if (h.am) {
+    TORCH_CHECK(h.am->scalar_type() == at::kByte && h.am->is_contiguous() && h.am->numel() >= B * 5408,
+                "am too small");
+    f.am = h.am->data_ptr<uint8_t>();
+  }
+  if (h.labels) {
+    need_cuda(*h.labels, h.labels_name);
+    TORCH_CHECK(h.labels->scalar_type() == at::kLong && h.labels->is_contiguous() &&
+                    h.labels->numel() == x.numel() / 784,
+                h.labels_name, " int64 [N]");
+    f.labels = h.labels->data_ptr<int64_t>();
+  }
+  if (h.state) {
+    const FrontState& st = *h.state;
+    TORCH_CHECK(st.s0w.numel() == 288 && st.s0b.numel() == 32, "optimizer state");
+    f.s0w = st.s0w.data_ptr<float>();
+    f.s0b = st.s0b.data_ptr<float>();
+    f.s1w = opt_ptr(st.s1w);
+    f.s1b = opt_ptr(st.s1b);
+  }
+  return f;
+}
+
+void check_lab_out(const at::Tensor& lab_out, int64_t B) {
+  need_cuda(lab_out, "lab_out");
+  TORCH_CHECK(lab_out.scalar_type() == at::kLong && lab_out.is_contiguous() && lab_out.numel() >= B,
+              "lab_out int64 [B]");
+}
+
 // lab_in / lab_out (optional, together): the shard's labels [N] and the batch's gathered
 // labels [B], written by the forward kernel (no separate index launch).
 void conv_fwd(const at::Tensor& x, const at::Tensor& idx, int64_t B, const at::Tensor& w, const at::Tensor& b,
               at::Tensor& y, at::Tensor& am, const OptT& lab_in, const OptT& lab_out) {
-  check_x(x);
-  check_params(w, b);
-  check_idx(idx, B);
-  need_f32(y, "y");
-  TORCH_CHECK(y.is_contiguous() && y.numel() >= B * 5408, "y too small");
-  TORCH_CHECK(am.scalar_type() == at::kByte && am.is_contiguous() && am.numel() >= B * 5408, "am too small");
+  FrontHas h;
+  h.idx = &idx, h.y = &y, h.am = &am;
   TORCH_CHECK(lab_in.has_value() == lab_out.has_value(), "lab_in and lab_out go together");
-  const int64_t* li = nullptr;
+  if (lab_in.has_value()) h.labels = &*lab_in, h.labels_name = "lab_in";
+  const Front f = front_args(x, w, b, B, h);
   int64_t* lo = nullptr;
   if (lab_in.has_value()) {
-    need_cuda(*lab_in, "lab_in");
-    need_cuda(*lab_out, "lab_out");
-    TORCH_CHECK(lab_in->scalar_type() == at::kLong && lab_in->is_contiguous() && lab_in->numel() == x.numel() / 784,
-                "lab_in int64 [N]");
-    TORCH_CHECK(lab_out->scalar_type() == at::kLong && lab_out->is_contiguous() && lab_out->numel() >= B,
-                "lab_out int64 [B]");
-    li = lab_in->data_ptr<int64_t>();
+    check_lab_out(*lab_out, B);
     lo = lab_out->data_ptr<int64_t>();
   }
-  check(sl::conv_fwd(x.data_ptr(), x.scalar_type() == at::kByte, idx.data_ptr<int64_t>(), 0, (int)B,
-                     w.data_ptr<float>(), b.data_ptr<float>(), y.data_ptr<float>(), am.data_ptr<uint8_t>(),
-                     cur_stream(), li, lo, nullptr),
+  ck(sl::conv_fwd(f.x, f.u8, f.idx, 0, (int)B, f.w, f.b, f.y, f.am, cur_stream(), f.labels, lo, nullptr),
         "conv_fwd");
 }
 
 ConvPending make_pending(const at::Tensor& slab, int64_t pB, at::Tensor& s0w, const OptT& s1w, at::Tensor& s0b,
-                             const OptT& s1b, SlOpt o) {
+                         const OptT& s1b, SlOpt o) {
   check_slab(slab, pB);
   TORCH_CHECK(pB >= 1, "pending batch");
   TORCH_CHECK(s0w.numel() == 288 && s0b.numel() == 32, "optimizer state");
-  return ConvPending{slab.data_ptr<float>(), (int)pB, s0w.data_ptr<float>(), fptr(s1w), s0b.data_ptr<float>(),
-                         fptr(s1b), o};
+  return ConvPending{slab.data_ptr<float>(), (int)pB, s0w.data_ptr<float>(), opt_ptr(s1w), s0b.data_ptr<float>(),
+                     opt_ptr(s1b), o};
 }
 
 // Forward with a deferred optimizer step applied in-kernel (FrontEngine, split modes):
@@ -172,22 +164,13 @@ void conv_fwd_pending(const at::Tensor& x, const at::Tensor& idx, int64_t B, con
                       at::Tensor& y, at::Tensor& am, const at::Tensor& lab_in, at::Tensor& lab_out,
                       const at::Tensor& pslab, int64_t pB, at::Tensor& s0w, const OptT& s1w, at::Tensor& s0b,
                       const OptT& s1b, OPT_ARGS) {
-  check_x(x);
-  check_params(w, b);
-  check_idx(idx, B);
-  need_f32(y, "y");
-  TORCH_CHECK(y.is_contiguous() && y.numel() >= B * 5408, "y too small");
-  TORCH_CHECK(am.scalar_type() == at::kByte && am.is_contiguous() && am.numel() >= B * 5408, "am too small");
-  need_cuda(lab_in, "lab_in");
-  need_cuda(lab_out, "lab_out");
-  TORCH_CHECK(lab_in.scalar_type() == at::kLong && lab_in.is_contiguous() && lab_in.numel() == x.numel() / 784,
-              "lab_in int64 [N]");
-  TORCH_CHECK(lab_out.scalar_type() == at::kLong && lab_out.is_contiguous() && lab_out.numel() >= B,
-              "lab_out int64 [B]");
+  FrontHas h;
+  h.idx = &idx, h.y = &y, h.am = &am, h.labels = &lab_in, h.labels_name = "lab_in";
+  const Front f = front_args(x, w, b, B, h);
+  check_lab_out(lab_out, B);
   const ConvPending p = make_pending(pslab, pB, s0w, s1w, s0b, s1b, OPT_PASS);
-  check(sl::conv_fwd(x.data_ptr(), x.scalar_type() == at::kByte, idx.data_ptr<int64_t>(), 0, (int)B,
-                     w.data_ptr<float>(), b.data_ptr<float>(), y.data_ptr<float>(), am.data_ptr<uint8_t>(),
-                     cur_stream(), lab_in.data_ptr<int64_t>(), lab_out.data_ptr<int64_t>(), &p),
+  ck(sl::conv_fwd(f.x, f.u8, f.idx, 0, (int)B, f.w, f.b, f.y, f.am, cur_stream(), f.labels,
+                     lab_out.data_ptr<int64_t>(), &p),
         "conv_fwd_pending");
 }
 
@@ -195,29 +178,27 @@ void conv_fwd_pending(const at::Tensor& x, const at::Tensor& idx, int64_t B, con
 void conv_local_step(const at::Tensor& x, const at::Tensor& idx, const at::Tensor& labels, int64_t B, at::Tensor& w,
                      at::Tensor& b, at::Tensor& slab, at::Tensor& loss_rows, at::Tensor& s0w, const OptT& s1w,
                      at::Tensor& s0b, const OptT& s1b, OPT_ARGS) {
-  check_x(x);
-  check_params(w, b);
-  check_idx(idx, B);
-  check_slab(slab, B);
-  need_cuda(labels, "labels");
-  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == x.numel() / 784, "labels int64 [N]");
+  const FrontState state{s0w, s1w, s0b, s1b};
+  FrontHas h;
+  h.idx = &idx, h.slab = &slab, h.labels = &labels, h.state = &state;
+  const Front f = front_args(x, w, b, B, h);
   need_f32(loss_rows, "loss_rows");
   TORCH_CHECK(loss_rows.numel() >= B, "loss_rows");
-  TORCH_CHECK(s0w.numel() == 288 && s0b.numel() == 32, "optimizer state");
-  check(sl::conv_local_step(x.data_ptr(), x.scalar_type() == at::kByte, idx.data_ptr<int64_t>(),
-                            labels.data_ptr<int64_t>(), (int)B, w.data_ptr<float>(), b.data_ptr<float>(),
-                            slab.data_ptr<float>(), loss_rows.data_ptr<float>(), s0w.data_ptr<float>(), fptr(s1w),
-                            s0b.data_ptr<float>(), fptr(s1b), OPT_PASS, cur_stream()),
+  ck(sl::conv_local_step(f.x, f.u8, f.idx, f.labels, (int)B, f.w, f.b, f.slab, loss_rows.data_ptr<float>(), f.s0w,
+                            f.s1w, f.s0b, f.s1b, OPT_PASS, cur_stream()),
         "conv_local_step");
 }
 
-struct EpochOpt {
-  int64_t kind;
-  double lr, beta1, beta2, eps, wd, momentum;
-};
+// the optimizer of a whole epoch: OptCfg::at(t) behind the launchers' callback
 SlOpt epoch_opt(void* ctx, int64_t t) {
-  const EpochOpt& e = *static_cast<const EpochOpt*>(ctx);
-  return make_opt(e.kind, e.lr, e.beta1, e.beta2, e.eps, e.wd, e.momentum, t, 0);
+  const OptCfg& e = *static_cast<const OptCfg*>(ctx);
+  if (e.kind == 2) TORCH_CHECK(t >= 1, "Adam step count must be >= 1");
+  return e.at(t);
+}
+
+void check_order(const at::Tensor& order) {
+  need_cuda(order, "order");
+  TORCH_CHECK(order.scalar_type() == at::kLong && order.is_contiguous() && order.dim() == 1, "order int64 [n]");
 }
 
 // A whole SISA local epoch: ceil(n/B) client steps over `order` (the last one partial, like
@@ -228,27 +209,23 @@ void conv_local_epoch(const at::Tensor& x, const at::Tensor& order, const at::Te
                       at::Tensor& w, at::Tensor& b, at::Tensor& slab, at::Tensor& loss_rows, at::Tensor& s0w,
                       const OptT& s1w, at::Tensor& s0b, const OptT& s1b, int64_t kind, double lr, double beta1,
                       double beta2, double eps, double wd, double momentum, int64_t t0, at::Tensor& ws) {
-  check_x(x);
-  check_params(w, b);
-  need_cuda(order, "order");
-  TORCH_CHECK(order.scalar_type() == at::kLong && order.is_contiguous() && order.dim() == 1, "order int64 [n]");
+  check_order(order);
   const int64_t n = order.numel();
   TORCH_CHECK(B >= 1 && B <= 4096, "batch size");
-  check_slab(slab, B);
-  need_cuda(labels, "labels");
-  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == x.numel() / 784, "labels int64 [N]");
+  const FrontState state{s0w, s1w, s0b, s1b};
+  FrontHas h;
+  h.slab = &slab, h.labels = &labels, h.state = &state;
+  const Front f = front_args(x, w, b, B, h);
   need_f32(loss_rows, "loss_rows");
   TORCH_CHECK(loss_rows.is_contiguous() && loss_rows.numel() >= n, "loss_rows [n]");
-  TORCH_CHECK(s0w.numel() == 288 && s0b.numel() == 32, "optimizer state");
   need_f32(ws, "ws");
   TORCH_CHECK(ws.is_contiguous(), "ws contiguous");
   TORCH_CHECK(kind == 1 || kind == 2, "local epoch: SGD-momentum or Adam");
   const hipStream_t st = cur_stream();
-  EpochOpt ctx{kind, lr, beta1, beta2, eps, wd, momentum};
-  check(sl::conv_local_epoch(x.data_ptr(), x.scalar_type() == at::kByte, order.data_ptr<int64_t>(), n, (int)B,
-                             labels.data_ptr<int64_t>(), w.data_ptr<float>(), b.data_ptr<float>(),
-                             s0w.data_ptr<float>(), fptr(s1w), s0b.data_ptr<float>(), fptr(s1b), ws.data_ptr<float>(),
-                             ws.numel(), loss_rows.data_ptr<float>(), &epoch_opt, &ctx, t0, st),
+  OptCfg ctx{(int)kind, lr, beta1, beta2, eps, wd, momentum};
+  ck(sl::conv_local_epoch(f.x, f.u8, order.data_ptr<int64_t>(), n, (int)B, f.labels, f.w, f.b, f.s0w, f.s1w, f.s0b,
+                             f.s1b, ws.data_ptr<float>(), ws.numel(), loss_rows.data_ptr<float>(), &epoch_opt, &ctx,
+                             t0, st),
         "conv_local_epoch");
 }
 
@@ -279,27 +256,23 @@ void conv_local_epoch_multi(py::list alices, int64_t B, int64_t kind, double lr,
     auto s1b = t[8].cast<OptT>();
     auto ws = t[9].cast<at::Tensor>();
     auto loss = t[10].cast<at::Tensor>();
-    check_x(x);
-    TORCH_CHECK(x.scalar_type() == at::kByte, "co-located epochs read uint8 shards");
-    check_params(w, b);
-    need_cuda(order, "order");
-    TORCH_CHECK(order.scalar_type() == at::kLong && order.is_contiguous() && order.dim() == 1, "order int64 [n]");
-    need_cuda(labels, "labels");
-    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.numel() == x.numel() / 784,
-                "labels int64 [N]");
-    TORCH_CHECK(s0w.numel() == 288 && s0b.numel() == 32, "optimizer state");
+    check_order(order);
+    const FrontState state{s0w, s1w, s0b, s1b};
+    FrontHas h;
+    h.labels = &labels, h.state = &state;
+    const Front f = front_args(x, w, b, B, h);
+    TORCH_CHECK(f.u8, "co-located epochs read uint8 shards");
     need_f32(ws, "ws");
     TORCH_CHECK(ws.is_contiguous() && ws.numel() >= 2 * B * 320 + 2 * 960, "ws");
     need_f32(loss, "loss_rows");
     TORCH_CHECK(loss.is_contiguous() && loss.numel() >= order.numel(), "loss_rows [n]");
-    al[a] = MultiAlice{x.data_ptr<uint8_t>(), order.data_ptr<int64_t>(), order.numel(), labels.data_ptr<int64_t>(),
-                           w.data_ptr<float>(), b.data_ptr<float>(), s0w.data_ptr<float>(), fptr(s1w),
-                           s0b.data_ptr<float>(), fptr(s1b), ws.data_ptr<float>(), ws.numel(),
-                           loss.data_ptr<float>(), t[11].cast<int64_t>()};
+    al[a] = MultiAlice{x.data_ptr<uint8_t>(), order.data_ptr<int64_t>(), order.numel(), f.labels, f.w, f.b, f.s0w,
+                       f.s1w, f.s0b, f.s1b, ws.data_ptr<float>(), ws.numel(), loss.data_ptr<float>(),
+                       t[11].cast<int64_t>()};
     if (kind == 2) TORCH_CHECK(al[a].s1w && al[a].s1b, "Adam second moments");
   }
-  EpochOpt ctx{kind, lr, beta1, beta2, eps, wd, momentum};
-  check(sl::conv_local_epoch_multi(al.data(), k, (int)B, &epoch_opt, &ctx, table.data_ptr(), table.numel(),
+  OptCfg ctx{(int)kind, lr, beta1, beta2, eps, wd, momentum};
+  ck(sl::conv_local_epoch_multi(al.data(), k, (int)B, &epoch_opt, &ctx, table.data_ptr(), table.numel(),
                                    cur_stream()),
         "conv_local_epoch_multi");
 }
@@ -336,54 +309,45 @@ void conv_fwd_multi(py::list alices, int64_t chunk) {
     set.d[a] = FrontFwdDesc{x.data_ptr<uint8_t>(), idx.has_value() ? idx->data_ptr<int64_t>() : nullptr, n,
                             w.data_ptr<float>(), b.data_ptr<float>(), y.data_ptr<float>()};
   }
-  check(sl::conv_fwd_multi(set, chunk, cur_stream()), "conv_fwd_multi");
+  ck(sl::conv_fwd_multi(set, chunk, cur_stream()), "conv_fwd_multi");
 }
 
-// Split-mode client backward: dW partials from the cut gradient, then reduce+optimizer.
+// Split-mode client backward: dW partials from the cut gradient, then reduce+optimizer
+// (conv_bwd_step), or deferred (conv_bwd_defer): this step's dW/db partials into `slab` (no update
+// launch); workgroup 0 stores the pending update of the previous step (pslab / pB / its opt), if any.
+Front bwd_args(const at::Tensor& dy, const at::Tensor& y, const at::Tensor& am, const at::Tensor& x,
+               const at::Tensor& idx, int64_t B, at::Tensor& w, at::Tensor& b, at::Tensor& slab, at::Tensor& s0w,
+               const OptT& s1w, at::Tensor& s0b, const OptT& s1b) {
+  need_f32(dy, "dy");
+  need_f32(y, "y");
+  TORCH_CHECK(dy.is_contiguous() && y.is_contiguous() && dy.numel() >= B * 5408 && y.numel() >= B * 5408, "dy/y");
+  const FrontState state{s0w, s1w, s0b, s1b};
+  FrontHas h;
+  h.idx = &idx, h.slab = &slab, h.am = &am, h.state = &state;
+  return front_args(x, w, b, B, h);
+}
+
 void conv_bwd_step(const at::Tensor& dy, const at::Tensor& y, const at::Tensor& am, const at::Tensor& x,
                    const at::Tensor& idx, int64_t B, at::Tensor& w, at::Tensor& b, at::Tensor& slab, at::Tensor& s0w,
                    const OptT& s1w, at::Tensor& s0b, const OptT& s1b, OPT_ARGS) {
-  check_x(x);
-  check_params(w, b);
-  check_idx(idx, B);
-  check_slab(slab, B);
-  need_f32(dy, "dy");
-  need_f32(y, "y");
-  TORCH_CHECK(dy.is_contiguous() && y.is_contiguous() && dy.numel() >= B * 5408 && y.numel() >= B * 5408, "dy/y");
-  TORCH_CHECK(am.scalar_type() == at::kByte && am.is_contiguous() && am.numel() >= B * 5408, "am");
-  TORCH_CHECK(s0w.numel() == 288 && s0b.numel() == 32, "optimizer state");
-  check(sl::conv_bwd_step(dy.data_ptr<float>(), y.data_ptr<float>(), am.data_ptr<uint8_t>(), x.data_ptr(),
-                          x.scalar_type() == at::kByte, idx.data_ptr<int64_t>(), (int)B, w.data_ptr<float>(),
-                          b.data_ptr<float>(), slab.data_ptr<float>(), s0w.data_ptr<float>(), fptr(s1w),
-                          s0b.data_ptr<float>(), fptr(s1b), OPT_PASS, cur_stream(), false, nullptr),
-        "conv_bwd_step");
+  const Front f = bwd_args(dy, y, am, x, idx, B, w, b, slab, s0w, s1w, s0b, s1b);
+  ck(sl::conv_bwd_step(dy.data_ptr<float>(), y.data_ptr<float>(), f.am, f.x, f.u8, f.idx, (int)B, f.w, f.b, f.slab,
+                       f.s0w, f.s1w, f.s0b, f.s1b, OPT_PASS, cur_stream(), false, nullptr),
+     "conv_bwd_step");
 }
 
-// Deferred-update backward: this step's dW/db partials into `slab` (no update launch);
-// workgroup 0 stores the pending update of the previous step (pslab / pB / its opt), if any.
 void conv_bwd_defer(const at::Tensor& dy, const at::Tensor& y, const at::Tensor& am, const at::Tensor& x,
                     const at::Tensor& idx, int64_t B, at::Tensor& w, at::Tensor& b, at::Tensor& slab, const OptT& pslab,
                     int64_t pB, at::Tensor& s0w, const OptT& s1w, at::Tensor& s0b, const OptT& s1b, OPT_ARGS) {
-  check_x(x);
-  check_params(w, b);
-  check_idx(idx, B);
-  check_slab(slab, B);
-  need_f32(dy, "dy");
-  need_f32(y, "y");
-  TORCH_CHECK(dy.is_contiguous() && y.is_contiguous() && dy.numel() >= B * 5408 && y.numel() >= B * 5408, "dy/y");
-  TORCH_CHECK(am.scalar_type() == at::kByte && am.is_contiguous() && am.numel() >= B * 5408, "am");
-  TORCH_CHECK(s0w.numel() == 288 && s0b.numel() == 32, "optimizer state");
-  const bool has = pslab.has_value() && pslab->defined();
+  const Front f = bwd_args(dy, y, am, x, idx, B, w, b, slab, s0w, s1w, s0b, s1b);
   ConvPending p{};
-  if (has) {
+  if (has(pslab)) {
     TORCH_CHECK(pslab->data_ptr<float>() != slab.data_ptr<float>(), "pending and new slabs must differ");
     p = make_pending(*pslab, pB, s0w, s1w, s0b, s1b, OPT_PASS);
   }
-  check(sl::conv_bwd_step(dy.data_ptr<float>(), y.data_ptr<float>(), am.data_ptr<uint8_t>(), x.data_ptr(),
-                          x.scalar_type() == at::kByte, idx.data_ptr<int64_t>(), (int)B, w.data_ptr<float>(),
-                          b.data_ptr<float>(), slab.data_ptr<float>(), s0w.data_ptr<float>(), fptr(s1w),
-                          s0b.data_ptr<float>(), fptr(s1b), SlOpt{}, cur_stream(), true, has ? &p : nullptr),
-        "conv_bwd_defer");
+  ck(sl::conv_bwd_step(dy.data_ptr<float>(), y.data_ptr<float>(), f.am, f.x, f.u8, f.idx, (int)B, f.w, f.b, f.slab,
+                       f.s0w, f.s1w, f.s0b, f.s1b, SlOpt{}, cur_stream(), true, has(pslab) ? &p : nullptr),
+     "conv_bwd_defer");
 }
 
 // U-shape head (Linear + CE) forward, data gradient and optimizer step in one launch.
@@ -401,10 +365,10 @@ void head_step(const at::Tensor& X, at::Tensor& W, const OptT& b, const at::Tens
   need_f32(dX, "dX");
   TORCH_CHECK(loss_rows.numel() >= M && dX.is_contiguous() && dX.numel() == M * K, "outputs");
   TORCH_CHECK(s0w.numel() == C * K && s0w.is_contiguous(), "state");
-  if (b.has_value() && b->defined()) TORCH_CHECK(b->numel() == C && s0b.has_value(), "bias state");
-  check(sl::head_step(X.data_ptr<float>(), W.data_ptr<float>(), fptr(b), y.data_ptr<int64_t>(), ignore, (float)scale,
-                      loss_rows.data_ptr<float>(), dX.data_ptr<float>(), s0w.data_ptr<float>(), fptr(s1w), fptr(s0b),
-                      fptr(s1b), (int)M, (int)K, (int)C, OPT_PASS, mask_dx, cur_stream()),
+  if (has(b)) TORCH_CHECK(b->numel() == C && s0b.has_value(), "bias state");
+  ck(sl::head_step(X.data_ptr<float>(), W.data_ptr<float>(), opt_ptr(b), y.data_ptr<int64_t>(), ignore, (float)scale,
+                      loss_rows.data_ptr<float>(), dX.data_ptr<float>(), s0w.data_ptr<float>(), opt_ptr(s1w), opt_ptr(s0b),
+                      opt_ptr(s1b), (int)M, (int)K, (int)C, OPT_PASS, mask_dx, cur_stream()),
         "head_step");
 }
 
@@ -413,7 +377,7 @@ void conv_apply(const at::Tensor& pslab, int64_t pB, at::Tensor& w, at::Tensor& 
                 at::Tensor& s0b, const OptT& s1b, OPT_ARGS) {
   check_params(w, b);
   const ConvPending p = make_pending(pslab, pB, s0w, s1w, s0b, s1b, OPT_PASS);
-  check(sl::conv_apply(p, w.data_ptr<float>(), b.data_ptr<float>(), cur_stream()), "conv_apply");
+  ck(sl::conv_apply(p, w.data_ptr<float>(), b.data_ptr<float>(), cur_stream()), "conv_apply");
 }
 
 // ---------------------------------------------------------------- linear
@@ -425,18 +389,11 @@ void linear_fwd(const at::Tensor& X, const at::Tensor& W, const OptT& bias, at::
   const int64_t M = X.size(0), K = X.size(1), N = W.size(0);
   TORCH_CHECK(W.size(1) == K && K % 4 == 0, "W must be [N,K] with K % 4 == 0");
   TORCH_CHECK(Y.size(0) == M && Y.size(1) == N, "Y must be [M,N]");
-  if (bias.has_value() && bias->defined()) TORCH_CHECK(bias->numel() == N && bias->is_contiguous(), "bias [N]");
-  float* wp = nullptr;
-  int64_t wn = 0;
-  if (ws.has_value() && ws->defined()) {
-    need_f32(*ws, "ws");
-    TORCH_CHECK(ws->is_contiguous(), "ws contiguous");
-    wp = ws->data_ptr<float>();
-    wn = ws->numel();
-  }
-  check(sl::linear_fwd(X.data_ptr<float>(), (int)X.stride(0), W.data_ptr<float>(), (int)W.stride(0),
+  if (has(bias)) TORCH_CHECK(bias->numel() == N && bias->is_contiguous(), "bias [N]");
+  const Ws w = opt_ws(ws);
+  ck(sl::linear_fwd(X.data_ptr<float>(), (int)X.stride(0), W.data_ptr<float>(), (int)W.stride(0),
                        Y.data_ptr<float>(), (int)Y.stride(0), (int)M, (int)N, (int)K,
-                       make_epi(bias, relu, drop_p, seed, col_off, dseed), wp, wn, cur_stream()),
+                       make_epi(bias, relu, drop_p, seed, col_off, dseed), w.p, w.n, cur_stream()),
         "linear_fwd");
 }
 
@@ -456,72 +413,52 @@ void linear_epilogue(const at::Tensor& P, const OptT& bias, at::Tensor& Y, bool 
     TORCH_CHECK(P.sizes() == Y.sizes(), "P/Y shape");
   }
   const int64_t M = Y.size(0), N = Y.size(1);
-  if (bias.has_value() && bias->defined()) TORCH_CHECK(bias->numel() == N, "bias [N]");
-  check(sl::linear_epilogue(P.data_ptr<float>(), (int)P.stride(P.dim() - 2), Y.data_ptr<float>(), (int)Y.stride(0),
+  if (has(bias)) TORCH_CHECK(bias->numel() == N, "bias [N]");
+  ck(sl::linear_epilogue(P.data_ptr<float>(), (int)P.stride(P.dim() - 2), Y.data_ptr<float>(), (int)Y.stride(0),
                             (int)M, (int)N, make_epi(bias, relu, drop_p, seed, col_off, dseed), S, slab, cur_stream()),
         "linear_epilogue");
 }
 
+// dX = mask(dZ . W): the skinny kernels (linear.hip), or (nn: many rows) the in-tree NN-layout MFMA
+// GEMM (gemm.hip), which also needs N % 4 == 0 and 16-byte aligned rows of dZ
+void dgrad(bool nn, const at::Tensor& dZ, const at::Tensor& W, const OptT& hprev, double scale, at::Tensor& dX,
+           const OptT& ws) {
+  need_2d(dZ, "dZ");
+  need_rows(W, "W");
+  need_2d(dX, "dX");
+  const int64_t M = dZ.size(0), N = dZ.size(1), K = W.size(1);
+  TORCH_CHECK(W.size(0) == N && K % 4 == 0 && (!nn || N % 4 == 0),
+              nn ? "W must be [N,K], N and K % 4 == 0" : "W must be [N,K] with K % 4 == 0");
+  TORCH_CHECK(dX.size(0) == M && dX.size(1) == K, "dX must be [M,K]");
+  if (nn) TORCH_CHECK(dZ.stride(0) % 4 == 0 && W.stride(0) % 4 == 0, "rows 16-B aligned");
+  const float* hp = nullptr;
+  int ldh = 0;
+  if (has(hprev)) {
+    need_2d(*hprev, "hprev");
+    TORCH_CHECK(hprev->size(0) == M && hprev->size(1) == K, "hprev shape");
+    hp = hprev->data_ptr<float>();
+    ldh = (int)hprev->stride(0);
+  }
+  const Ws w = opt_ws(ws);
+  const float *dz = dZ.data_ptr<float>(), *wt = W.data_ptr<float>();
+  float* dx = dX.data_ptr<float>();
+  const int ldz = (int)dZ.stride(0), ldw = (int)W.stride(0), ldx = (int)dX.stride(0);
+  if (nn)
+    ck(sl::gemm_nn_dgrad(dz, ldz, wt, ldw, hp, ldh, (float)scale, dx, ldx, (int)M, (int)N, (int)K, w.p, w.n,
+                            cur_stream()),
+          "gemm_nn_dgrad");
+  else
+    ck(sl::linear_dgrad(dz, ldz, wt, ldw, hp, ldh, (float)scale, dx, ldx, w.p, w.n, (int)M, (int)N, (int)K,
+                           cur_stream()),
+          "linear_dgrad");
+}
 void linear_dgrad(const at::Tensor& dZ, const at::Tensor& W, const OptT& hprev, double scale, at::Tensor& dX,
                   const OptT& ws) {
-  need_2d(dZ, "dZ");
-  need_rows(W, "W");
-  need_2d(dX, "dX");
-  const int64_t M = dZ.size(0), N = dZ.size(1), K = W.size(1);
-  TORCH_CHECK(W.size(0) == N && K % 4 == 0, "W must be [N,K]");
-  TORCH_CHECK(dX.size(0) == M && dX.size(1) == K, "dX must be [M,K]");
-  const float* hp = nullptr;
-  int ldh = 0;
-  if (hprev.has_value() && hprev->defined()) {
-    need_2d(*hprev, "hprev");
-    TORCH_CHECK(hprev->size(0) == M && hprev->size(1) == K, "hprev shape");
-    hp = hprev->data_ptr<float>();
-    ldh = (int)hprev->stride(0);
-  }
-  float* wp = nullptr;
-  int64_t wn = 0;
-  if (ws.has_value() && ws->defined()) {
-    need_f32(*ws, "ws");
-    TORCH_CHECK(ws->is_contiguous(), "ws contiguous");
-    wp = ws->data_ptr<float>();
-    wn = ws->numel();
-  }
-  check(sl::linear_dgrad(dZ.data_ptr<float>(), (int)dZ.stride(0), W.data_ptr<float>(), (int)W.stride(0), hp, ldh,
-                         (float)scale, dX.data_ptr<float>(), (int)dX.stride(0), wp, wn, (int)M, (int)N, (int)K,
-                         cur_stream()),
-        "linear_dgrad");
+  dgrad(false, dZ, W, hprev, scale, dX, ws);
 }
-
-// the data gradient of many rows on the in-tree NN-layout MFMA GEMM (csrc/gemm.hip)
 void gemm_nn_dgrad(const at::Tensor& dZ, const at::Tensor& W, const OptT& hprev, double scale, at::Tensor& dX,
                    const OptT& ws) {
-  need_2d(dZ, "dZ");
-  need_rows(W, "W");
-  need_2d(dX, "dX");
-  const int64_t M = dZ.size(0), N = dZ.size(1), K = W.size(1);
-  TORCH_CHECK(W.size(0) == N && K % 4 == 0 && N % 4 == 0, "W must be [N,K], N and K % 4 == 0");
-  TORCH_CHECK(dX.size(0) == M && dX.size(1) == K, "dX must be [M,K]");
-  TORCH_CHECK(dZ.stride(0) % 4 == 0 && W.stride(0) % 4 == 0, "rows 16-B aligned");
-  const float* hp = nullptr;
-  int ldh = 0;
-  if (hprev.has_value() && hprev->defined()) {
-    need_2d(*hprev, "hprev");
-    TORCH_CHECK(hprev->size(0) == M && hprev->size(1) == K, "hprev shape");
-    hp = hprev->data_ptr<float>();
-    ldh = (int)hprev->stride(0);
-  }
-  float* wp = nullptr;
-  int64_t wn = 0;
-  if (ws.has_value() && ws->defined()) {
-    need_f32(*ws, "ws");
-    TORCH_CHECK(ws->is_contiguous(), "ws contiguous");
-    wp = ws->data_ptr<float>();
-    wn = ws->numel();
-  }
-  check(sl::gemm_nn_dgrad(dZ.data_ptr<float>(), (int)dZ.stride(0), W.data_ptr<float>(), (int)W.stride(0), hp, ldh,
-                          (float)scale, dX.data_ptr<float>(), (int)dX.stride(0), (int)M, (int)N, (int)K, wp, wn,
-                          cur_stream()),
-        "gemm_nn_dgrad");
+  dgrad(true, dZ, W, hprev, scale, dX, ws);
 }
 
 void linear_wgrad_opt(const at::Tensor& dZ, const at::Tensor& A, at::Tensor& W, at::Tensor& s0, const OptT& s1,
@@ -533,13 +470,13 @@ void linear_wgrad_opt(const at::Tensor& dZ, const at::Tensor& A, at::Tensor& W, 
   const int64_t M = dZ.size(0), N = dZ.size(1), K = A.size(1);
   TORCH_CHECK(A.size(0) == M && W.size(0) == N && W.size(1) == K && K % 4 == 0, "shapes");
   TORCH_CHECK(s0.sizes() == W.sizes() && s0.stride(0) == W.stride(0), "s0 like W");
-  if (s1.has_value() && s1->defined()) TORCH_CHECK(s1->sizes() == W.sizes() && s1->stride(0) == W.stride(0), "s1");
-  if (kind == 2) TORCH_CHECK(s1.has_value() && s1->defined(), "Adam needs s1");
-  if (bias.has_value() && bias->defined())
+  if (has(s1)) TORCH_CHECK(s1->sizes() == W.sizes() && s1->stride(0) == W.stride(0), "s1");
+  if (kind == 2) TORCH_CHECK(has(s1), "Adam needs s1");
+  if (has(bias))
     TORCH_CHECK(bias->numel() == N && sb0.has_value() && sb0->numel() == N, "bias state");
-  check(sl::linear_wgrad_opt(dZ.data_ptr<float>(), (int)dZ.stride(0), A.data_ptr<float>(), (int)A.stride(0),
-                             W.data_ptr<float>(), (int)W.stride(0), s0.data_ptr<float>(), fptr(s1), fptr(bias),
-                             fptr(sb0), fptr(sb1), (int)M, (int)N, (int)K, OPT_PASS, cur_stream()),
+  ck(sl::linear_wgrad_opt(dZ.data_ptr<float>(), (int)dZ.stride(0), A.data_ptr<float>(), (int)A.stride(0),
+                             W.data_ptr<float>(), (int)W.stride(0), s0.data_ptr<float>(), opt_ptr(s1), opt_ptr(bias),
+                             opt_ptr(sb0), opt_ptr(sb1), (int)M, (int)N, (int)K, OPT_PASS, cur_stream()),
         "linear_wgrad_opt");
 }
 
@@ -549,7 +486,7 @@ void opt_flat(at::Tensor& p, const at::Tensor& g, at::Tensor& s0, const OptT& s1
   need_f32(s0, "s0");
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && s0.is_contiguous(), "contiguous");
   TORCH_CHECK(g.numel() == p.numel() && s0.numel() == p.numel(), "sizes");
-  check(sl::opt_flat(p.data_ptr<float>(), g.data_ptr<float>(), s0.data_ptr<float>(), fptr(s1), p.numel(), OPT_PASS,
+  ck(sl::opt_flat(p.data_ptr<float>(), g.data_ptr<float>(), s0.data_ptr<float>(), opt_ptr(s1), p.numel(), OPT_PASS,
                      cur_stream()),
         "opt_flat");
 }
@@ -589,14 +526,14 @@ void multi_opt(const std::vector<at::Tensor>& ps, const std::vector<at::Tensor>&
   TORCH_CHECK(kind != 2 || s1s.size() == k, "multi_opt: Adam needs one s1 per parameter");
   if (k == 0) return;
   const float* gsc = nullptr;
-  if (gscale.has_value() && gscale->defined()) {
+  if (has(gscale)) {
     need_f32(*gscale, "gscale");
     TORCH_CHECK(gscale->numel() >= 1 && gscale->device() == ps[0].device(), "gscale: a float on the parameters' device");
     gsc = gscale->data_ptr<float>();
   }
   const SlOpt o = OPT_PASS;
   const hipStream_t st = cur_stream();
-  auto launch = [&](const sl::MultiOptTable& tab) { check(sl::multi_opt(tab, o, gsc, st), "multi_opt"); };
+  auto launch = [&](const sl::MultiOptTable& tab) { ck(sl::multi_opt(tab, o, gsc, st), "multi_opt"); };
   sl::MultiOptTable tab{};
   for (size_t i = 0; i < k; ++i) {
     need_f32(ps[i], "param");
@@ -630,7 +567,7 @@ void grad_norm(const std::vector<at::Tensor>& gs, double max_norm, at::Tensor& o
   const hipStream_t st = cur_stream();
   float* slots = ws.data_ptr<float>();
   auto launch = [&](const sl::MultiOptTable& tab) {
-    check(sl::grad_sumsq(tab, slots, st), "grad_sumsq");
+    ck(sl::grad_sumsq(tab, slots, st), "grad_sumsq");
     slots += tab.chunks;
   };
   sl::MultiOptTable tab{};
@@ -639,19 +576,14 @@ void grad_norm(const std::vector<at::Tensor>& gs, double max_norm, at::Tensor& o
     table_add(tab, sl::MultiOptTensor{nullptr, g.data_ptr<float>(), nullptr, nullptr, g.numel(), 0}, launch);
   }
   if (tab.k) launch(tab);
-  check(sl::grad_norm_finish(ws.data_ptr<float>(), total, (float)max_norm, out3.data_ptr<float>(), st), "grad_norm_finish");
+  ck(sl::grad_norm_finish(ws.data_ptr<float>(), total, (float)max_norm, out3.data_ptr<float>(), st), "grad_norm_finish");
 }
 
 // ---------------------------------------------------------------- general 3x3 conv (conv2d.hip)
 // x [B, Cin, H, W], w [Cout, Cin, 3, 3], y / dy / am [B, Cout, Hy, Wy]: contiguous, fp32 (am
 // uint8), on the current device, each under 2 GB (the kernels index with 32-bit byte offsets).
-void conv_need(const at::Tensor& t, const at::Tensor& like, const char* name, bool u8 = false) {
-  need_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == (u8 ? at::kByte : at::kFloat), name, u8 ? " must be uint8" : " must be float32");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.device() == like.device() && t.get_device() == c10::hip::current_device(), name,
-              " must be on the current device");
-  TORCH_CHECK(t.numel() * (int64_t)t.element_size() < (int64_t(1) << 31), name, " must be under 2 GB");
+void conv_need(const at::Tensor& t, const char* name, bool u8 = false) {
+  need_dense(t, u8 ? at::kByte : at::kFloat, name, true);
 }
 
 sl::Conv2dShape conv_shape(at::IntArrayRef x, at::IntArrayRef w, int64_t pad, bool relu, int64_t pool) {
@@ -679,35 +611,35 @@ void conv_check_y(const at::Tensor& t, const sl::Conv2dShape& s, const char* nam
 void conv3x3_fwd(const at::Tensor& x, const at::Tensor& w, const OptT& bias, at::Tensor& y, const OptT& am,
                  int64_t pad, bool relu, int64_t pool) {
   const sl::Conv2dShape s = conv_shape(x.sizes(), w.sizes(), pad, relu, pool);
-  conv_need(x, x, "x");
-  conv_need(w, x, "w");
-  conv_need(y, x, "y");
+  conv_need(x, "x");
+  conv_need(w, "w");
+  conv_need(y, "y");
   conv_check_y(y, s, "y");
-  const bool has_b = bias.has_value() && bias->defined();
+  const bool has_b = has(bias);
   if (has_b) {
-    conv_need(*bias, x, "bias");
+    conv_need(*bias, "bias");
     TORCH_CHECK(bias->numel() == s.Cout, "bias [Cout]");
   }
-  TORCH_CHECK((am.has_value() && am->defined()) == (bool)s.pool, "am goes with pooling");
+  TORCH_CHECK(has(am) == (bool)s.pool, "am goes with pooling");
   if (s.pool) {
-    conv_need(*am, x, "am", true);
+    conv_need(*am, "am", true);
     conv_check_y(*am, s, "am");
   }
-  check(sl::conv3x3_fwd(x.data_ptr<float>(), w.data_ptr<float>(), has_b ? bias->data_ptr<float>() : nullptr,
+  ck(sl::conv3x3_fwd(x.data_ptr<float>(), w.data_ptr<float>(), has_b ? bias->data_ptr<float>() : nullptr,
                         y.data_ptr<float>(), s.pool ? am->data_ptr<uint8_t>() : nullptr, s, cur_stream()),
         "conv3x3_fwd");
 }
 
 // dy, y (, am) of the forward -> the operands of both backward kernels
-const uint8_t* conv_check_bwd(const at::Tensor& dy, const at::Tensor& y, const OptT& am, const at::Tensor& like,
+const uint8_t* conv_check_bwd(const at::Tensor& dy, const at::Tensor& y, const OptT& am,
                               const sl::Conv2dShape& s) {
-  conv_need(dy, like, "dy");
-  conv_need(y, like, "y");
+  conv_need(dy, "dy");
+  conv_need(y, "y");
   conv_check_y(dy, s, "dy");
   conv_check_y(y, s, "y");
-  TORCH_CHECK((am.has_value() && am->defined()) == (bool)s.pool, "am goes with pooling");
+  TORCH_CHECK(has(am) == (bool)s.pool, "am goes with pooling");
   if (!s.pool) return nullptr;
-  conv_need(*am, like, "am", true);
+  conv_need(*am, "am", true);
   conv_check_y(*am, s, "am");
   return am->data_ptr<uint8_t>();
 }
@@ -715,10 +647,10 @@ const uint8_t* conv_check_bwd(const at::Tensor& dy, const at::Tensor& y, const O
 void conv3x3_dgrad(const at::Tensor& dy, const at::Tensor& y, const OptT& am, const at::Tensor& w, at::Tensor& dx,
                    int64_t pad, bool relu, int64_t pool) {
   const sl::Conv2dShape s = conv_shape(dx.sizes(), w.sizes(), pad, relu, pool);
-  conv_need(w, dy, "w");
-  conv_need(dx, dy, "dx");
-  const uint8_t* a = conv_check_bwd(dy, y, am, dy, s);
-  check(sl::conv3x3_dgrad(dy.data_ptr<float>(), y.data_ptr<float>(), a, w.data_ptr<float>(), dx.data_ptr<float>(), s,
+  conv_need(w, "w");
+  conv_need(dx, "dx");
+  const uint8_t* a = conv_check_bwd(dy, y, am, s);
+  ck(sl::conv3x3_dgrad(dy.data_ptr<float>(), y.data_ptr<float>(), a, w.data_ptr<float>(), dx.data_ptr<float>(), s,
                           cur_stream()),
         "conv3x3_dgrad");
 }
@@ -731,17 +663,17 @@ int64_t conv3x3_wgrad_ws(std::vector<int64_t> x_shape, std::vector<int64_t> w_sh
 void conv3x3_wgrad(const at::Tensor& dy, const at::Tensor& y, const OptT& am, const at::Tensor& x, at::Tensor& ws,
                    at::Tensor& dw, const OptT& db, int64_t pad, bool relu, int64_t pool) {
   const sl::Conv2dShape s = conv_shape(x.sizes(), dw.sizes(), pad, relu, pool);
-  conv_need(x, dy, "x");
-  conv_need(dw, dy, "dw");
-  conv_need(ws, dy, "workspace");
+  conv_need(x, "x");
+  conv_need(dw, "dw");
+  conv_need(ws, "workspace");
   TORCH_CHECK(ws.numel() >= (int64_t)sl::conv3x3_wgrad_slabs(s) * s.Cout * (s.Cin * 9 + 1), "conv3x3_wgrad workspace");
-  const bool has_b = db.has_value() && db->defined();
+  const bool has_b = has(db);
   if (has_b) {
-    conv_need(*db, dy, "db");
+    conv_need(*db, "db");
     TORCH_CHECK(db->numel() == s.Cout, "db [Cout]");
   }
-  const uint8_t* a = conv_check_bwd(dy, y, am, dy, s);
-  check(sl::conv3x3_wgrad(dy.data_ptr<float>(), y.data_ptr<float>(), a, x.data_ptr<float>(), ws.data_ptr<float>(),
+  const uint8_t* a = conv_check_bwd(dy, y, am, s);
+  ck(sl::conv3x3_wgrad(dy.data_ptr<float>(), y.data_ptr<float>(), a, x.data_ptr<float>(), ws.data_ptr<float>(),
                           dw.data_ptr<float>(), has_b ? db->data_ptr<float>() : nullptr, s, cur_stream()),
         "conv3x3_wgrad");
 }
@@ -769,7 +701,7 @@ sl::GroupNormShape gn_shape(at::IntArrayRef x, int64_t groups, double eps, bool 
 }
 
 void gn_check_y(const at::Tensor& t, const at::Tensor& x, const sl::GroupNormShape& s, const char* name, bool u8) {
-  conv_need(t, x, name, u8);
+  conv_need(t, name, u8);
   if (s.pool) {
     TORCH_CHECK(t.dim() == 4 && t.size(0) == s.B && t.size(1) == s.C && t.size(2) == s.Hy && t.size(3) == s.Wy, name,
                 " must be [B, C, H / 2, W / 2]");
@@ -778,24 +710,24 @@ void gn_check_y(const at::Tensor& t, const at::Tensor& x, const sl::GroupNormSha
   }
 }
 
-void gn_check_vec(const at::Tensor& t, const at::Tensor& x, int64_t numel, const char* name) {
-  conv_need(t, x, name);
+void gn_check_vec(const at::Tensor& t, int64_t numel, const char* name) {
+  conv_need(t, name);
   TORCH_CHECK(t.numel() == numel, name, " has the wrong number of elements");
 }
 
 // the affine's two vectors: both or neither
-bool gn_affine(const OptT& w, const OptT& b, const at::Tensor& x, int C, const char* wn, const char* bn) {
-  const bool has_w = w.has_value() && w->defined(), has_b = b.has_value() && b->defined();
+bool gn_affine(const OptT& w, const OptT& b, int C, const char* wn, const char* bn) {
+  const bool has_w = has(w), has_b = has(b);
   TORCH_CHECK(has_w == has_b, "group_norm: ", wn, " and ", bn, " go together");
   if (has_w) {
-    gn_check_vec(*w, x, C, wn);
-    gn_check_vec(*b, x, C, bn);
+    gn_check_vec(*w, C, wn);
+    gn_check_vec(*b, C, bn);
   }
   return has_w;
 }
 
 const uint8_t* gn_check_am(const OptT& am, const at::Tensor& x, const sl::GroupNormShape& s) {
-  TORCH_CHECK((am.has_value() && am->defined()) == (bool)s.pool, "am goes with pooling");
+  TORCH_CHECK(has(am) == (bool)s.pool, "am goes with pooling");
   if (!s.pool) return nullptr;
   gn_check_y(*am, x, s, "am", true);
   return am->data_ptr<uint8_t>();
@@ -804,13 +736,13 @@ const uint8_t* gn_check_am(const OptT& am, const at::Tensor& x, const sl::GroupN
 void group_norm_fwd(const at::Tensor& x, const OptT& w, const OptT& b, at::Tensor& y, at::Tensor& mean,
                     at::Tensor& rstd, const OptT& am, int64_t groups, double eps, bool relu, int64_t pool) {
   const sl::GroupNormShape s = gn_shape(x.sizes(), groups, eps, relu, pool);
-  conv_need(x, x, "x");
+  conv_need(x, "x");
   gn_check_y(y, x, s, "y", false);
-  gn_check_vec(mean, x, (int64_t)s.B * s.G, "mean");
-  gn_check_vec(rstd, x, (int64_t)s.B * s.G, "rstd");
-  const bool affine = gn_affine(w, b, x, s.C, "weight", "bias");
+  gn_check_vec(mean, (int64_t)s.B * s.G, "mean");
+  gn_check_vec(rstd, (int64_t)s.B * s.G, "rstd");
+  const bool affine = gn_affine(w, b, s.C, "weight", "bias");
   const uint8_t* a = gn_check_am(am, x, s);
-  check(sl::group_norm_fwd(x.data_ptr<float>(), affine ? w->data_ptr<float>() : nullptr,
+  ck(sl::group_norm_fwd(x.data_ptr<float>(), affine ? w->data_ptr<float>() : nullptr,
                            affine ? b->data_ptr<float>() : nullptr, y.data_ptr<float>(), mean.data_ptr<float>(),
                            rstd.data_ptr<float>(), const_cast<uint8_t*>(a), s, cur_stream()),
         "group_norm_fwd");
@@ -820,25 +752,25 @@ void group_norm_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor&
                     const OptT& w, const OptT& b, const OptT& am, const OptT& dx, const OptT& ws, const OptT& dw,
                     const OptT& db, int64_t groups, bool relu, int64_t pool) {
   const sl::GroupNormShape s = gn_shape(x.sizes(), groups, 0.0, relu, pool);
-  conv_need(x, x, "x");
+  conv_need(x, "x");
   gn_check_y(dy, x, s, "dy", false);
-  gn_check_vec(mean, x, (int64_t)s.B * s.G, "mean");
-  gn_check_vec(rstd, x, (int64_t)s.B * s.G, "rstd");
-  const bool affine = gn_affine(w, b, x, s.C, "weight", "bias");
-  TORCH_CHECK(gn_affine(dw, db, x, s.C, "dweight", "dbias") == affine, "group_norm: dweight / dbias go with the affine");
-  const bool has_ws = ws.has_value() && ws->defined();
+  gn_check_vec(mean, (int64_t)s.B * s.G, "mean");
+  gn_check_vec(rstd, (int64_t)s.B * s.G, "rstd");
+  const bool affine = gn_affine(w, b, s.C, "weight", "bias");
+  TORCH_CHECK(gn_affine(dw, db, s.C, "dweight", "dbias") == affine, "group_norm: dweight / dbias go with the affine");
+  const bool has_ws = has(ws);
   TORCH_CHECK(has_ws == affine, "group_norm: the workspace goes with the affine");
   if (affine) {
-    conv_need(*ws, x, "workspace");
+    conv_need(*ws, "workspace");
     TORCH_CHECK(ws->numel() >= (int64_t)s.B * s.C * 2, "group_norm workspace: [B, C, 2]");
   }
-  const bool need_dx = dx.has_value() && dx->defined();
+  const bool need_dx = has(dx);
   if (need_dx) {
-    conv_need(*dx, x, "dx");
+    conv_need(*dx, "dx");
     TORCH_CHECK(dx->sizes() == x.sizes(), "dx must have x's shape");
   }
   const uint8_t* a = gn_check_am(am, x, s);
-  check(sl::group_norm_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+  ck(sl::group_norm_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
                            affine ? w->data_ptr<float>() : nullptr, affine ? b->data_ptr<float>() : nullptr, a,
                            need_dx ? dx->data_ptr<float>() : nullptr, affine ? ws->data_ptr<float>() : nullptr,
                            affine ? dw->data_ptr<float>() : nullptr, affine ? db->data_ptr<float>() : nullptr, s,
@@ -849,11 +781,9 @@ void group_norm_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor&
 // ---------------------------------------------------------------- cut codec (cutcodec.hip)
 // x / y [R, K] fp32, payload int8 [R, K] (8 bits) or uint8 [R, ceil(K / 2)] (4 bits), scales fp32
 // [R, ceil(K / group)]: contiguous, on the current device.  R, K < 2^31; the kernels index in 64 bits.
-void cut_need(const at::Tensor& t, at::ScalarType ty, const char* name, const char* tyname) {
-  need_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == ty, name, " must be ", tyname);
-  TORCH_CHECK(t.dim() == 2 && t.is_contiguous(), name, " must be 2-D and contiguous");
-  TORCH_CHECK(t.get_device() == c10::hip::current_device(), name, " must be on the current device");
+void cut_need(const at::Tensor& t, at::ScalarType ty, const char* name) {
+  need_dense(t, ty, name);
+  TORCH_CHECK(t.dim() == 2, name, " must be 2-D");
 }
 
 sl::CutShape cut_shape(int64_t R, int64_t K, int64_t bits, int64_t group, uint64_t seed, bool stochastic) {
@@ -869,9 +799,9 @@ sl::CutShape cut_shape(int64_t R, int64_t K, int64_t bits, int64_t group, uint64
 }
 
 void cut_check_wire(const at::Tensor& payload, const at::Tensor& scales, const sl::CutShape& s) {
-  if (s.bits == 8) cut_need(payload, at::kChar, "payload", "int8");
-  else cut_need(payload, at::kByte, "payload", "uint8");
-  cut_need(scales, at::kFloat, "scales", "float32");
+  if (s.bits == 8) cut_need(payload, at::kChar, "payload");
+  else cut_need(payload, at::kByte, "payload");
+  cut_need(scales, at::kFloat, "scales");
   const int64_t kb = s.bits == 8 ? s.K : ((int64_t)s.K + 1) / 2;
   TORCH_CHECK(payload.size(0) == s.R && payload.size(1) == kb, "payload must be [R, K] (8 bits) or [R, ceil(K / 2)] (4 bits)");
   TORCH_CHECK(scales.size(0) == s.R && scales.size(1) == s.ng, "scales must be [R, ceil(K / group)]");
@@ -879,27 +809,27 @@ void cut_check_wire(const at::Tensor& payload, const at::Tensor& scales, const s
 
 void cut_pack(const at::Tensor& x, at::Tensor& payload, at::Tensor& scales, int64_t bits, int64_t group, uint64_t seed,
               bool stochastic) {
-  cut_need(x, at::kFloat, "x", "float32");
+  cut_need(x, at::kFloat, "x");
   const sl::CutShape s = cut_shape(x.size(0), x.size(1), bits, group, seed, stochastic);
   cut_check_wire(payload, scales, s);
   TORCH_CHECK(payload.device() == x.device() && scales.device() == x.device(), "cut_pack: tensors on different devices");
-  check(sl::cut_pack(x.data_ptr<float>(), payload.data_ptr(), scales.data_ptr<float>(), s, cur_stream()), "cut_pack");
+  ck(sl::cut_pack(x.data_ptr<float>(), payload.data_ptr(), scales.data_ptr<float>(), s, cur_stream()), "cut_pack");
 }
 
 void cut_unpack(const at::Tensor& payload, const at::Tensor& scales, at::Tensor& y, int64_t bits, int64_t group) {
-  cut_need(y, at::kFloat, "y", "float32");
+  cut_need(y, at::kFloat, "y");
   const sl::CutShape s = cut_shape(y.size(0), y.size(1), bits, group, 0, false);
   cut_check_wire(payload, scales, s);
   TORCH_CHECK(payload.device() == y.device() && scales.device() == y.device(), "cut_unpack: tensors on different devices");
-  check(sl::cut_unpack(payload.data_ptr(), scales.data_ptr<float>(), y.data_ptr<float>(), s, cur_stream()), "cut_unpack");
+  ck(sl::cut_unpack(payload.data_ptr(), scales.data_ptr<float>(), y.data_ptr<float>(), s, cur_stream()), "cut_unpack");
 }
 
 void cut_roundtrip(const at::Tensor& x, at::Tensor& y, int64_t bits, int64_t group, uint64_t seed, bool stochastic) {
-  cut_need(x, at::kFloat, "x", "float32");
-  cut_need(y, at::kFloat, "y", "float32");
+  cut_need(x, at::kFloat, "x");
+  cut_need(y, at::kFloat, "y");
   TORCH_CHECK(y.sizes() == x.sizes() && y.device() == x.device(), "cut_roundtrip: y must have x's shape and device");
   const sl::CutShape s = cut_shape(x.size(0), x.size(1), bits, group, seed, stochastic);
-  check(sl::cut_roundtrip(x.data_ptr<float>(), y.data_ptr<float>(), s, cur_stream()), "cut_roundtrip");
+  ck(sl::cut_roundtrip(x.data_ptr<float>(), y.data_ptr<float>(), s, cur_stream()), "cut_roundtrip");
 }
 
 // ---------------------------------------------------------------- loss / metrics
@@ -913,13 +843,13 @@ void softmax_ce(const at::Tensor& x, const at::Tensor& y, int64_t ignore, double
   TORCH_CHECK(loss_rows.numel() >= M, "loss_rows");
   float* dp = nullptr;
   int ldd = 0;
-  if (d.has_value() && d->defined()) {
+  if (has(d)) {
     need_2d(*d, "dlogits");
     TORCH_CHECK(d->size(0) == M && d->size(1) == C, "dlogits shape");
     dp = d->data_ptr<float>();
     ldd = (int)d->stride(0);
   }
-  check(sl::softmax_ce(x.data_ptr<float>(), (int)x.stride(0), y.data_ptr<int64_t>(), ignore, (float)scale,
+  ck(sl::softmax_ce(x.data_ptr<float>(), (int)x.stride(0), y.data_ptr<int64_t>(), ignore, (float)scale,
                        loss_rows.data_ptr<float>(), dp, ldd, (int)M, (int)C, cur_stream()),
         "softmax_ce");
 }
@@ -931,7 +861,7 @@ void relu_mask(const at::Tensor& d, const at::Tensor& h, double scale, at::Tenso
   TORCH_CHECK(d.is_contiguous() && h.is_contiguous() && out.is_contiguous() && d.numel() == h.numel() &&
                   out.numel() == d.numel(),
               "relu_mask: contiguous tensors of one size");
-  check(sl::relu_mask(d.data_ptr<float>(), h.data_ptr<float>(), (float)scale, out.data_ptr<float>(), d.numel(),
+  ck(sl::relu_mask(d.data_ptr<float>(), h.data_ptr<float>(), (float)scale, out.data_ptr<float>(), d.numel(),
                       cur_stream()),
         "relu_mask");
 }
@@ -941,7 +871,7 @@ void eval_counters(const at::Tensor& x, const at::Tensor& y, int64_t omit, at::T
   TORCH_CHECK(y.scalar_type() == at::kLong && y.numel() == x.size(0) && y.is_contiguous(), "labels");
   TORCH_CHECK(counters.scalar_type() == at::kLong && counters.numel() >= 6 && counters.is_contiguous(), "counters");
   need_cuda(counters, "counters");
-  check(sl::eval_counters(x.data_ptr<float>(), (int)x.stride(0), y.data_ptr<int64_t>(), omit,
+  ck(sl::eval_counters(x.data_ptr<float>(), (int)x.stride(0), y.data_ptr<int64_t>(), omit,
                           reinterpret_cast<unsigned long long*>(counters.data_ptr<int64_t>()), (int)x.size(0),
                           (int)x.size(1), cur_stream()),
         "eval_counters");
@@ -956,7 +886,7 @@ int64_t linear_fwd_partial(const at::Tensor& X, const at::Tensor& W, at::Tensor&
   const int64_t M = X.size(0), K = X.size(1), N = W.size(0);
   TORCH_CHECK(W.size(1) == K && K % 4 == 0, "W must be [N,K] with K % 4 == 0");
   int S = 1;
-  check(sl::linear_fwd_partial(X.data_ptr<float>(), (int)X.stride(0), W.data_ptr<float>(), (int)W.stride(0), (int)M,
+  ck(sl::linear_fwd_partial(X.data_ptr<float>(), (int)X.stride(0), W.data_ptr<float>(), (int)W.stride(0), (int)M,
                                (int)N, (int)K, ws.data_ptr<float>(), ws.numel(), (int)max_split, &S, cur_stream()),
         "linear_fwd_partial");
   return S;
@@ -980,7 +910,7 @@ void server_head3(const at::Tensor& P2, const OptT& b2, bool relu2, double drop2
   need_cuda(y, "labels");
   TORCH_CHECK(G >= 1 && C % G == 0, "C % groups");
   TORCH_CHECK(y.scalar_type() == at::kLong && y.numel() == M * G && y.is_contiguous(), "labels int64 [M, groups]");
-  if (gscale.has_value() && gscale->defined()) {
+  if (has(gscale)) {
     need_f32(*gscale, "gscale");
     TORCH_CHECK(gscale->is_contiguous() && gscale->numel() == M * G, "gscale [M, groups]");
   }
@@ -992,11 +922,11 @@ void server_head3(const at::Tensor& P2, const OptT& b2, bool relu2, double drop2
   TORCH_CHECK(dlog.is_contiguous() && dlog.size(0) == M && dlog.size(1) == C, "dlog [M,C]");
   need_f32(loss_rows, "loss_rows");
   TORCH_CHECK(loss_rows.numel() >= M * G, "loss_rows [M, groups]");
-  check(sl::server_head3(P2.data_ptr<float>(), (int)S2, M * N2, make_epi(b2, relu2, drop2, seed2, 0, dseed2),
-                         W3.data_ptr<float>(), (int)W3.stride(0), fptr(b3), y.data_ptr<int64_t>(), ignore,
+  ck(sl::server_head3(P2.data_ptr<float>(), (int)S2, M * N2, make_epi(b2, relu2, drop2, seed2, 0, dseed2),
+                         W3.data_ptr<float>(), (int)W3.stride(0), opt_ptr(b3), y.data_ptr<int64_t>(), ignore,
                          (float)scale, h2.data_ptr<float>(), dlog.data_ptr<float>(), dz2.data_ptr<float>(),
                          loss_rows.data_ptr<float>(), ws.data_ptr<float>(), ws.numel(), (int)M, (int)N2, (int)C,
-                         cur_stream(), nullptr, (int)G, fptr(gscale)),
+                         cur_stream(), nullptr, (int)G, opt_ptr(gscale)),
         "server_head3");
 }
 
@@ -1034,15 +964,15 @@ void wgrad_group(const std::vector<py::tuple>& layers, int64_t M, const OptT& xn
     d.W = W.data_ptr<float>();
     d.ldw = (int)W.stride(0);
     d.s0 = s0.data_ptr<float>();
-    d.s1 = fptr(s1);
-    d.bias = fptr(bias);
-    d.sb0 = fptr(sb0);
-    d.sb1 = fptr(sb1);
+    d.s1 = opt_ptr(s1);
+    d.bias = opt_ptr(bias);
+    d.sb0 = opt_ptr(sb0);
+    d.sb1 = opt_ptr(sb1);
     d.N = (int)N;
     d.K = (int)K;
   }
-  if (xn.has_value() && xn->defined()) {
-    TORCH_CHECK(pn.has_value() && pn->defined(), "pn needed with xn");
+  if (has(xn)) {
+    TORCH_CHECK(has(pn), "pn needed with xn");
     need_rows(*xn, "xn");
     need_f32(*pn, "pn");
     const int64_t K0 = g.d[0].K, N0 = g.d[0].N, mn = xn->size(0);
@@ -1053,7 +983,7 @@ void wgrad_group(const std::vector<py::tuple>& layers, int64_t M, const OptT& xn
     g.mn = (int)mn;
     g.pn = pn->data_ptr<float>();
   }
-  check(sl::wgrad_group(g, (int)M, OPT_PASS, cur_stream()), "wgrad_group");
+  ck(sl::wgrad_group(g, (int)M, OPT_PASS, cur_stream()), "wgrad_group");
 }
 
 }  // namespace
@@ -1065,6 +995,7 @@ void sl_register_resident(pybind11::module& m);
 void sl_register_hybrid(pybind11::module& m);
 void sl_register_vanilla(pybind11::module& m);
 void sl_register_ushape(pybind11::module& m);
+void sl_register_handoff(pybind11::module& m);
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "splitlearning_amd gfx950 (MI355X) HIP kernels";
@@ -1075,6 +1006,7 @@ PYBIND11_MODULE(_C, m) {
   sl_register_hybrid(m);
   sl_register_vanilla(m);
   sl_register_ushape(m);
+  sl_register_handoff(m);
   m.def("conv_fwd", &conv_fwd);
   m.def("conv_local_step", &conv_local_step);
   m.def("conv_bwd_step", &conv_bwd_step);
@@ -1136,53 +1068,5 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_gemm_nn_splits", [](int s) { sl::g_nn_splits = s < 0 ? 0 : s; });
   m.def("set_gemm_nn_form", [](int wm) { sl::g_nn_wm = (wm == 2 || wm == 4) ? wm : 0; });
   m.def("set_gemm_nt_splits", [](int s) { sl::g_nt_splits = s < 0 ? 0 : s; });
-  // hand-off stress test (csrc/handoff.hip, tests/test_handoff_gpu.py): G workgroups x R rounds
-  // of the persistent kernels' publication primitive in `mode`; returns {mismatching words,
-  // rounds completed by the slowest workgroup, error word, kernel ms, first mismatch [7]...}
-  m.def("handoff_stress", [](int64_t G, int64_t P, int64_t R, int64_t nsrc, int64_t src_stride, int64_t mode,
-                             double busy_us, double timeout_s) {
-    sl::HoArgs a{};
-    a.P = (int)P;
-    a.R = (int)R;
-    a.nsrc = (int)nsrc;
-    a.src_stride = (int)src_stride;
-    a.mode = (int)mode;
-    const std::string why = sl::handoff_check(a, (int)G);
-    TORCH_CHECK(why.empty(), "handoff_stress: ", why);
-    int dev = 0, khz = 0;
-    TORCH_CHECK(hipGetDevice(&dev) == hipSuccess, "device");
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
-    auto fo = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, dev);
-    auto io = fo.dtype(at::kInt);
-    at::Tensor D = at::zeros({G * P}, fo), S = at::zeros({G * sl::kHoScratchF4 * 4}, fo);
-    at::Tensor cnt = at::zeros({2 * 8 * sl::kHoStride}, io), bad = at::zeros({G}, io), done = at::zeros({G}, io);
-    at::Tensor first = at::zeros({8}, io), err = at::zeros({1}, io);
-    a.D = D.data_ptr<float>();
-    a.scratch = S.data_ptr<float>();
-    a.cnt = reinterpret_cast<unsigned*>(cnt.data_ptr<int>());
-    a.bad = reinterpret_cast<unsigned*>(bad.data_ptr<int>());
-    a.done = reinterpret_cast<unsigned*>(done.data_ptr<int>());
-    a.first = reinterpret_cast<unsigned*>(first.data_ptr<int>());
-    a.err = err.data_ptr<int>();
-    a.timeout = (int64_t)(timeout_s * 1000.0 * khz);
-    a.busy_ticks = (int)(busy_us * khz / 1000.0);
-    const hipStream_t st = cur_stream();
-    hipEvent_t e0, e1;
-    TORCH_CHECK(hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess, "events");
-    TORCH_CHECK(hipEventRecord(e0, st) == hipSuccess, "event");
-    check(sl::handoff_stress_launch(a, (int)G, st), "handoff_stress");
-    TORCH_CHECK(hipEventRecord(e1, st) == hipSuccess, "event");
-    TORCH_CHECK(hipEventSynchronize(e1) == hipSuccess, "handoff_stress sync");
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    const int64_t nbad = bad.to(at::kLong).sum().item<int64_t>();
-    const int64_t rmin = done.min().item<int>();
-    std::vector<int64_t> f(7);
-    auto fc = first.cpu();
-    for (int i = 0; i < 7; ++i) f[i] = (int64_t)(uint32_t)fc.data_ptr<int>()[i];
-    return pybind11::make_tuple(nbad, rmin, err.item<int>(), (double)ms, f);
-  });
   m.attr("arch") = "gfx950";
 }

@@ -8,12 +8,12 @@
 // rendezvous, timeouts and failure detection stay with the control plane).  It links the
 // same librccl.so.1 that PyTorch-ROCm loads (one RCCL instance per process).
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
 #include <rccl/rccl.h>
 
 #include <cstring>
 #include <string>
 
+#include "args.h"
 #include "comm.h"
 #include "ipc_p2p.h"
 
@@ -54,7 +54,7 @@ void TpComm::allreduce_sum_f32(float* p, size_t n, hipStream_t st) {
 
 namespace {
 
-hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
+using sl::args::cur_stream;
 
 ncclDataType_t dtype_of(const at::Tensor& t) {
   switch (t.scalar_type()) {
@@ -76,28 +76,28 @@ void need(const at::Tensor& t) {
 void allreduce_sum(sl::TpComm& c, at::Tensor& t) {
   need(t);
   if (t.scalar_type() == at::kFloat) {
-    c.allreduce_sum_f32(t.data_ptr<float>(), (size_t)t.numel(), stream());
+    c.allreduce_sum_f32(t.data_ptr<float>(), (size_t)t.numel(), cur_stream());
     return;
   }
-  SL_NCCL(ncclAllReduce(t.data_ptr(), t.data_ptr(), t.numel(), dtype_of(t), ncclSum, c.get(), stream()));
+  SL_NCCL(ncclAllReduce(t.data_ptr(), t.data_ptr(), t.numel(), dtype_of(t), ncclSum, c.get(), cur_stream()));
 }
 void broadcast(sl::TpComm& c, at::Tensor& t, int root) {
   need(t);
-  SL_NCCL(ncclBroadcast(t.data_ptr(), t.data_ptr(), t.numel(), dtype_of(t), root, c.get(), stream()));
+  SL_NCCL(ncclBroadcast(t.data_ptr(), t.data_ptr(), t.numel(), dtype_of(t), root, c.get(), cur_stream()));
 }
 void all_gather(sl::TpComm& c, at::Tensor& out, const at::Tensor& in) {
   need(out);
   need(in);
   TORCH_CHECK(out.numel() == in.numel() * c.size() && out.scalar_type() == in.scalar_type(), "all_gather sizes");
-  SL_NCCL(ncclAllGather(in.data_ptr(), out.data_ptr(), in.numel(), dtype_of(in), c.get(), stream()));
+  SL_NCCL(ncclAllGather(in.data_ptr(), out.data_ptr(), in.numel(), dtype_of(in), c.get(), cur_stream()));
 }
 void send(sl::TpComm& c, const at::Tensor& t, int peer) {
   need(t);
-  SL_NCCL(ncclSend(t.data_ptr(), t.numel(), dtype_of(t), peer, c.get(), stream()));
+  SL_NCCL(ncclSend(t.data_ptr(), t.numel(), dtype_of(t), peer, c.get(), cur_stream()));
 }
 void recv(sl::TpComm& c, at::Tensor& t, int peer) {
   need(t);
-  SL_NCCL(ncclRecv(t.data_ptr(), t.numel(), dtype_of(t), peer, c.get(), stream()));
+  SL_NCCL(ncclRecv(t.data_ptr(), t.numel(), dtype_of(t), peer, c.get(), cur_stream()));
 }
 
 py::bytes unique_id() {
@@ -136,7 +136,7 @@ void sl_register_comm(py::module& m) {
       .def("allreduce_sum", [](sl::IpcAllReduce& a, at::Tensor& t) {
         need(t);
         TORCH_CHECK(t.scalar_type() == at::kFloat, "IpcAllReduce: f32");
-        a.allreduce_sum_f32(t.data_ptr<float>(), (size_t)t.numel(), stream());
+        a.allreduce_sum_f32(t.data_ptr<float>(), (size_t)t.numel(), cur_stream());
       })
       .def("error", &sl::IpcAllReduce::error)
       .def("host_error", &sl::IpcAllReduce::host_error)
@@ -160,12 +160,12 @@ void sl_register_comm(py::module& m) {
       .def("send", [](sl::IpcChannel& a, const at::Tensor& t, int peer) {
         need(t);
         TORCH_CHECK(t.nbytes() % 16 == 0, "IpcChannel: messages are whole 16-byte units");
-        a.send(static_cast<const float*>(t.data_ptr()), (int64_t)(t.nbytes() / 4), peer, stream());
+        a.send(static_cast<const float*>(t.data_ptr()), (int64_t)(t.nbytes() / 4), peer, cur_stream());
       })
       .def("recv", [](sl::IpcChannel& a, at::Tensor& t, int peer) {
         need(t);
         TORCH_CHECK(t.nbytes() % 16 == 0, "IpcChannel: messages are whole 16-byte units");
-        a.recv(static_cast<float*>(t.data_ptr()), (int64_t)(t.nbytes() / 4), peer, stream());
+        a.recv(static_cast<float*>(t.data_ptr()), (int64_t)(t.nbytes() / 4), peer, cur_stream());
       })
       .def("error", &sl::IpcChannel::error)
       .def("host_error", &sl::IpcChannel::host_error)

@@ -11,6 +11,7 @@
 // is no separate collate/convert kernel) and its 8x9 weights in LDS and writes its part of
 // the pooled, NCHW-flattened [5408] activation plus a 2-bit argmax for backward.
 #include "common.h"
+#include "kernels.h"
 
 #include <algorithm>
 #include <vector>

@@ -20,43 +20,26 @@
 // counts as the Python path, so results are bit-identical to it
 // (tests/test_graphs_gpu.py::test_native_server_epoch_matches_python).
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
 
 #include <algorithm>
 #include <string>
 
+#include "args.h"
 #include "comm.h"
 #include "common.h"
 #include "fused.h"
 #include "host.h"
-
-namespace sl {
-hipError_t linear_fwd(const float* X, int ldx, const float* W, int ldw, float* Y, int ldy, int M, int N, int K,
-                      Epi e, float* ws, int64_t ws_elems, hipStream_t st);
-hipError_t linear_dgrad(const float* dZ, int ldz, const float* W, int ldw, const float* hprev, int ldh,
-                        float scale, float* dX, int ldx, float* ws, int64_t ws_elems, int M, int N, int K,
-                        hipStream_t st);
-hipError_t linear_epilogue(const float* P, int ldp, float* Y, int ldy, int M, int N, Epi e, int S, int64_t slab,
-                           hipStream_t st);
-hipError_t linear_fwd_partial(const float* X, int ldx, const float* W, int ldw, int M, int N, int K, float* ws,
-                              int64_t ws_elems, int max_split, int* S_out, hipStream_t st);
-}  // namespace sl
+#include "kernels.h"
 
 namespace py = pybind11;
 
 namespace {
 
-void ck(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e)); }
-
-at::Tensor get(const py::dict& d, const char* k) {
-  TORCH_CHECK(d.contains(k), "ServerEpoch: missing '", k, "'");
-  return d[k].cast<at::Tensor>();
-}
-
-struct Layer {
-  at::Tensor W, b, s0, s1, sb0, sb1;   // s1 / sb1 undefined for SGD
-  int N = 0, K = 0;
-};
+using sl::args::ck;
+using sl::args::cur_stream;
+using sl::args::dict_tensor;
+using Layer = sl::args::TailLayer;
+constexpr const char* kWho = "ServerEpoch";
 
 class ServerEpoch {
  public:
@@ -64,37 +47,15 @@ class ServerEpoch {
   // p1, p2 (dropout), col_off1, row2 (fc2 row-parallel), comm (TpComm | None),
   // workspaces: pn, p2ws, fwdws, dgws, headws, h1, h2, dz1, dz2, dlog (each for B rows).
   explicit ServerEpoch(const py::dict& cfg) {
-    auto layers = cfg["layers"].cast<std::vector<py::dict>>();
-    TORCH_CHECK(layers.size() == 3, "ServerEpoch drives the 3-layer server tail");
-    for (int i = 0; i < 3; ++i) {
-      Layer& L = L_[i];
-      const py::dict& d = layers[i];
-      L.W = get(d, "W");
-      L.b = get(d, "b");
-      L.s0 = get(d, "s0");
-      L.sb0 = get(d, "sb0");
-      if (d.contains("s1") && !d["s1"].is_none()) L.s1 = get(d, "s1");
-      if (d.contains("sb1") && !d["sb1"].is_none()) L.sb1 = get(d, "sb1");
-      for (const at::Tensor* t : {&L.W, &L.b, &L.s0, &L.sb0}) {
-        TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(), "layer tensors: f32 GPU");
-      }
-      TORCH_CHECK(L.W.dim() == 2 && L.W.size(1) % 4 == 0, "W [N, K] with K % 4 == 0");
-      L.N = (int)L.W.size(0);
-      L.K = (int)L.W.size(1);
-      TORCH_CHECK(L.b.numel() == L.N && L.s0.sizes() == L.W.sizes() && L.sb0.numel() == L.N, "layer state shapes");
+    L_ = sl::args::read_tail_layers(cfg, kWho);
+    for (const Layer& L : L_) {
+      TORCH_CHECK(L.K % 4 == 0, "W [N, K] with K % 4 == 0");
+      TORCH_CHECK(L.sb0.numel() == L.N, "layer state shapes");
     }
-    TORCH_CHECK(L_[1].K == L_[0].N && L_[2].K == L_[1].N, "layer chain shapes");
     TORCH_CHECK(L_[1].N % 4 == 0, "fc2 width % 4");
-    kind_ = cfg["kind"].cast<int>();
-    TORCH_CHECK(kind_ == 1 || kind_ == 2, "SGD-momentum or Adam");
-    if (kind_ == 2)
+    opt_ = sl::args::read_opt(cfg);
+    if (opt_.kind == 2)
       for (auto& L : L_) TORCH_CHECK(L.s1.defined() && L.sb1.defined() && L.s1.sizes() == L.W.sizes(), "Adam v");
-    lr_ = cfg["lr"].cast<double>();
-    beta1_ = cfg["beta1"].cast<double>();
-    beta2_ = cfg["beta2"].cast<double>();
-    eps_ = cfg["eps"].cast<double>();
-    wd_ = cfg["wd"].cast<double>();
-    mom_ = cfg["momentum"].cast<double>();
     p1_ = cfg["p1"].cast<double>();
     p2_ = cfg["p2"].cast<double>();
     col_off1_ = cfg["col_off1"].cast<int>();
@@ -114,16 +75,16 @@ class ServerEpoch {
     TORCH_CHECK(G_ >= 1 && L_[2].N % G_ == 0, "fc3 width % groups");
     B_ = cfg["B"].cast<int>();
     TORCH_CHECK(B_ >= 1 && B_ <= 64, "batch 1..64 (look-ahead row chunks of the wgrad kernel)");
-    pn_ = get(cfg, "pn");
-    p2ws_ = get(cfg, "p2ws");
-    fwdws_ = get(cfg, "fwdws");
-    dgws_ = get(cfg, "dgws");
-    headws_ = get(cfg, "headws");
-    h1_ = get(cfg, "h1");
-    h2_ = get(cfg, "h2");
-    dz1_ = get(cfg, "dz1");
-    dz2_ = get(cfg, "dz2");
-    dlog_ = get(cfg, "dlog");
+    pn_ = dict_tensor(cfg, "pn", kWho);
+    p2ws_ = dict_tensor(cfg, "p2ws", kWho);
+    fwdws_ = dict_tensor(cfg, "fwdws", kWho);
+    dgws_ = dict_tensor(cfg, "dgws", kWho);
+    headws_ = dict_tensor(cfg, "headws", kWho);
+    h1_ = dict_tensor(cfg, "h1", kWho);
+    h2_ = dict_tensor(cfg, "h2", kWho);
+    dz1_ = dict_tensor(cfg, "dz1", kWho);
+    dz2_ = dict_tensor(cfg, "dz2", kWho);
+    dlog_ = dict_tensor(cfg, "dlog", kWho);
     const int64_t S1 = (L_[0].K + 255) / 256;
     TORCH_CHECK(pn_.numel() >= S1 * B_ * L_[0].N, "pn workspace");
     TORCH_CHECK(h1_.numel() >= (int64_t)B_ * L_[0].N && dz1_.numel() >= (int64_t)B_ * L_[0].N, "h1 / dz1");
@@ -214,7 +175,7 @@ class ServerEpoch {
     const int M = st.M;
     const int K1 = L_[0].K, N1 = L_[0].N, N2 = L_[1].N;
     const int64_t S1 = (K1 + 255) / 256;
-    const hipStream_t sm = stream();
+    const hipStream_t sm = cur_stream();
     const float* x = st.acts->data_ptr<float>() + st.s * K1;
     float* h1 = h1_.data_ptr<float>();
     float* P2 = p2ws_.data_ptr<float>();
@@ -250,7 +211,7 @@ class ServerEpoch {
   void finish(Step& st, at::Tensor& loss_rows) {
     const int M = st.M;
     const int K1 = L_[0].K, N1 = L_[0].N, N2 = L_[1].N, C = L_[2].N;
-    const hipStream_t sm = stream();
+    const hipStream_t sm = cur_stream();
     const int64_t n = st.acts->size(0);
     const float* X = st.acts->data_ptr<float>();
     const float* x = X + st.s * K1;
@@ -289,7 +250,7 @@ class ServerEpoch {
   void wgrad(Step& st) {
     const int M = st.M;
     const int K1 = L_[0].K, N1 = L_[0].N, N2 = L_[1].N, C = L_[2].N;
-    const hipStream_t sm = stream();
+    const hipStream_t sm = cur_stream();
     const int64_t n = st.acts->size(0);
     const float* X = st.acts->data_ptr<float>();
     const float* x = X + st.s * K1;
@@ -314,10 +275,10 @@ class ServerEpoch {
       d.W = L.W.data_ptr<float>();
       d.ldw = L.K;
       d.s0 = L.s0.data_ptr<float>();
-      d.s1 = L.s1.defined() ? L.s1.data_ptr<float>() : nullptr;
+      d.s1 = L.v();
       d.bias = L.b.data_ptr<float>();
       d.sb0 = L.sb0.data_ptr<float>();
-      d.sb1 = L.sb1.defined() ? L.sb1.data_ptr<float>() : nullptr;
+      d.sb1 = L.vb();
       d.N = L.N;
       d.K = L.K;
     }
@@ -328,8 +289,7 @@ class ServerEpoch {
       g.mn = B_;
       g.pn = pn_.data_ptr<float>();
     }
-    const SlOpt o = sl::make_opt_raw(kind_, lr_, beta1_, beta2_, eps_, wd_, mom_, st.t, nullptr);
-    ck(sl::wgrad_group(g, M, o, sm), "wgrad_group");
+    ck(sl::wgrad_group(g, M, opt_.at(st.t), sm), "wgrad_group");
     st.next_pre = next_full;
   }
 
@@ -343,14 +303,14 @@ class ServerEpoch {
     if (a == nullptr) return false;
     if ((int64_t)M * L_[1].N > a->cap() || (int64_t)M * sl::head3_slices(L_[1].N) > sl::kIpcFlags) return false;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(stream(), &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(cur_stream(), &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
   }
 
   void allreduce(float* p, size_t n) {
     if (comm_ != nullptr)
-      comm_->allreduce_sum_f32(p, n, stream());   // the attached peer-mapped path or RCCL
+      comm_->allreduce_sum_f32(p, n, cur_stream());   // the attached peer-mapped path or RCCL
     else if (ipc_ != nullptr)
-      ipc_->allreduce_sum_f32(p, n, stream());
+      ipc_->allreduce_sum_f32(p, n, cur_stream());
     else
       TORCH_CHECK(false, "ServerEpoch: a row-parallel fc2 without a communicator");
   }
@@ -372,9 +332,9 @@ class ServerEpoch {
   int batch() const { return B_; }
 
  private:
-  Layer L_[3];
-  int kind_ = 2;
-  double lr_ = 0, beta1_ = 0, beta2_ = 0, eps_ = 0, wd_ = 0, mom_ = 0, p1_ = 0, p2_ = 0;
+  std::array<Layer, 3> L_;
+  sl::args::OptCfg opt_;
+  double p1_ = 0, p2_ = 0;
   int col_off1_ = 0;
   bool row2_ = false;
   sl::TpComm* comm_ = nullptr;
@@ -385,7 +345,6 @@ class ServerEpoch {
   int G_ = 1;
   const float* gscale_ = nullptr;
   at::Tensor pn_, p2ws_, fwdws_, dgws_, headws_, h1_, h2_, dz1_, dz2_, dlog_;
-  static hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
 };
 
 // Single-process emulation of the tensor-parallel server epoch: T shard executors (each

@@ -19,6 +19,7 @@
 // Rows are padded (fp32 +4 floats, bf16 +8 halves) so the 16 rows a lane group reads land on
 // different banks.  Requires K % 4 == 0 and 16-byte aligned rows (host checks).
 #include "common.h"
+#include "kernels.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -427,9 +428,6 @@ gemm_nn_f32x32_kernel(const float* __restrict__ A, int lda, const float* __restr
     }
 }
 
-hipError_t dgrad_reduce(const float* P, int S, int64_t slab, const float* hprev, int ldh, float scale, float* out,
-                        int ldo, int M, int K, hipStream_t st);
-
 // dX[M, K] = mask(dZ[M, R] . W[R, K]): 256 x 128 tiles when they fill the chip, else 128 x 128
 // tiles split over the reduction (the choice below).
 hipError_t gemm_nn_dgrad(const float* dZ, int ldz, const float* W, int ldw, const float* hprev, int ldh, float scale,
@@ -473,9 +471,6 @@ hipError_t gemm_nn_dgrad(const float* dZ, int ldz, const float* W, int ldw, cons
   if (S > 1) return dgrad_reduce(ws, S, (int64_t)M * K, hprev, ldh, scale, dX, ldx, M, K, st);
   return hipGetLastError();
 }
-
-hipError_t linear_epilogue(const float* P, int ldp, float* Y, int ldy, int M, int N, Epi e, int S, int64_t slab,
-                           hipStream_t st);
 
 // S > 1: split-K over S slices into ws ([S][M][N], >= S M N floats), then one reduce +
 // epilogue launch.

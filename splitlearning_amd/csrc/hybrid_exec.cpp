@@ -8,7 +8,6 @@
 // fc1 tile runs of the workgroups and the counters' arrival counts, zeroes the counters (in
 // the launch), launches cooperatively and reads the kernel's error word once.
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
 
 #include <string>
 #include <vector>
@@ -20,14 +19,7 @@ namespace py = pybind11;
 
 namespace {
 
-at::Tensor hy_get(const py::dict& d, const char* k) {
-  TORCH_CHECK(d.contains(k) && !d[k].is_none(), "HybridEpoch: missing '", k, "'");
-  return d[k].cast<at::Tensor>();
-}
-
-struct HyLayer {
-  at::Tensor W, b, s0, s1, sb0, sb1;
-};
+using Layer = sl::args::TailLayer;
 
 class HybridEpoch {
  public:
@@ -35,33 +27,17 @@ class HybridEpoch {
   // beta1 / beta2 / eps / wd / momentum, p1 / p2, col_off1, B, ipc (IpcAllReduce or None),
   // timeout_s, workgroups (0: one per CU, a multiple of 8)
   explicit HybridEpoch(const py::dict& cfg) {
-    auto layers = cfg["layers"].cast<std::vector<py::dict>>();
-    TORCH_CHECK(layers.size() == 3, "HybridEpoch drives the 3-layer server tail");
-    kind_ = cfg["kind"].cast<int>();
-    TORCH_CHECK(kind_ == 1 || kind_ == 2, "SGD-momentum or Adam");
-    for (int i = 0; i < 3; ++i) {
-      HyLayer& L = L_[i];
-      const py::dict& d = layers[i];
-      L.W = hy_get(d, "W");
-      L.b = hy_get(d, "b");
-      L.s0 = hy_get(d, "s0");
-      L.sb0 = hy_get(d, "sb0");
-      if (kind_ == 2) {
-        L.s1 = hy_get(d, "s1");
-        L.sb1 = hy_get(d, "sb1");
+    opt_ = sl::args::read_opt(cfg);
+    L_ = sl::args::read_tail_layers(cfg, "HybridEpoch");
+    // s1 / sb1 only for Adam: required then, not read otherwise
+    for (Layer& L : L_) {
+      if (opt_.kind != 2) {
+        L.s1 = L.sb1 = at::Tensor();
+        continue;
       }
-      for (const at::Tensor* t : {&L.W, &L.b, &L.s0, &L.sb0, &L.s1, &L.sb1})
-        if (t->defined())
-          TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(), "layer tensors: f32 GPU");
-      TORCH_CHECK(L.W.dim() == 2 && L.s0.sizes() == L.W.sizes() && L.b.numel() == L.W.size(0), "layer shapes");
+      TORCH_CHECK(L.s1.defined() && L.sb1.defined(), "HybridEpoch: missing 's1' / 'sb1' (Adam)");
+      TORCH_CHECK(sl::args::dense_f32(L.s1) && sl::args::dense_f32(L.sb1), "HybridEpoch: layer tensors: f32 GPU");
     }
-    TORCH_CHECK(L_[1].W.size(1) == L_[0].W.size(0) && L_[2].W.size(1) == L_[1].W.size(0), "layer chain shapes");
-    lr_ = cfg["lr"].cast<double>();
-    beta1_ = cfg["beta1"].cast<double>();
-    beta2_ = cfg["beta2"].cast<double>();
-    eps_ = cfg["eps"].cast<double>();
-    wd_ = cfg["wd"].cast<double>();
-    mom_ = cfg["momentum"].cast<double>();
     p1_ = cfg["p1"].cast<double>();
     p2_ = cfg["p2"].cast<double>();
     col_off1_ = cfg["col_off1"].cast<int>();
@@ -73,9 +49,7 @@ class HybridEpoch {
     dev_ = dev.index();
     int cus = 0;
     TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_) == hipSuccess, "CU count");
-    int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev_) != hipSuccess || khz <= 0) khz = 100000;
-    clock_khz_ = khz;
+    clock_khz_ = sl::args::clock_khz(dev_);
 
     sl::HyArgs& a = a_;
     a = sl::HyArgs{};
@@ -100,7 +74,7 @@ class HybridEpoch {
     // shard's streamed state is larger than the 256 MB Infinity Cache (TP = 1), write-through
     // when it fits (csrc/hybrid.hip kStW ..); cfg "nt_stores" (0 / 1) overrides for the A/B
     {
-      const int64_t state = (int64_t)L_[0].W.numel() * 4 * (kind_ == 2 ? 3 : 2);
+      const int64_t state = (int64_t)L_[0].W.numel() * 4 * (opt_.kind == 2 ? 3 : 2);
       const int o = cfg.contains("nt_stores") && !cfg["nt_stores"].is_none() ? cfg["nt_stores"].cast<int>() : -1;
       a.ntst = o >= 0 ? o : (state > (256LL << 20) ? 1 : 0);
     }
@@ -152,18 +126,10 @@ class HybridEpoch {
       a.err = err_.data_ptr<int>();
       a.tab = tab_.data_ptr<int>();
       a.timeout = (int64_t)(timeout_s_ * 1000.0 * clock_khz_);
-      auto setL = [](sl::ResLayer& r, HyLayer& L) {
-        r.W = L.W.data_ptr<float>();
-        r.b = L.b.data_ptr<float>();
-        r.m = L.s0.data_ptr<float>();
-        r.mb = L.sb0.data_ptr<float>();
-        r.v = L.s1.defined() ? L.s1.data_ptr<float>() : nullptr;
-        r.vb = L.sb1.defined() ? L.sb1.data_ptr<float>() : nullptr;
-      };
-      setL(a.L1, L_[0]);
-      setL(a.L2, L_[1]);
-      setL(a.L3, L_[2]);
-      a.o = sl::make_opt_raw(kind_, lr_, beta1_, beta2_, eps_, wd_, mom_, 0, nullptr);
+      a.L1 = sl::host::res_layer(L_[0]);
+      a.L2 = sl::host::res_layer(L_[1]);
+      a.L3 = sl::host::res_layer(L_[2]);
+      a.o = opt_.at(0);
       if (ipc_ != nullptr) {
         TORCH_CHECK(ipc_->opened(), "HybridEpoch: the peer-mapped region is not open");
         a.ipc.T = ipc_->size();
@@ -213,9 +179,7 @@ class HybridEpoch {
       TORCH_CHECK((int64_t)step_rows->size() == S && acts.size(0) == S * B_,
                   "step_rows: one row count per step, acts exactly S * B rows");
     std::vector<float> adam(4 * S, 0.f);
-    sl::host::fill_adam(adam, 4, 0, t, [&](int64_t step) {
-      return sl::make_opt_raw(kind_, lr_, beta1_, beta2_, eps_, wd_, mom_, step, nullptr);
-    });
+    sl::host::fill_adam(adam, 4, 0, t, [&](int64_t step) { return opt_.at(step); });
     sl::host::fill_rows(adam, 4, 2, -1, [&](int64_t i) {
       const int64_t rows = step_rows.has_value() ? (*step_rows)[i] : B_;
       TORCH_CHECK(rows >= 1 && rows <= B_, "step_rows: 1 .. B rows per step");
@@ -242,7 +206,7 @@ class HybridEpoch {
       ta = trace_all->data_ptr<int64_t>();
       tan = (int)(trace_all->numel() / (16LL * a_.G));
     }
-    const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    const hipStream_t st = sl::args::cur_stream();
     const int e = sl::host::run_chunks("hybrid", a_.err, err_, st, S, max_steps_, fault_step_,
                                           [&](int64_t s0, int64_t n, int fault) {
       sl::HyArgs a = a_;
@@ -320,9 +284,10 @@ class HybridEpoch {
     return "";
   }
 
-  HyLayer L_[3];
-  int kind_ = 2, col_off1_ = 0, B_ = 16, dev_ = 0, clock_khz_ = 100000;
-  double lr_ = 0, beta1_ = 0, beta2_ = 0, eps_ = 0, wd_ = 0, mom_ = 0, p1_ = 0, p2_ = 0, timeout_s_ = 30.0;
+  std::array<Layer, 3> L_;
+  sl::args::OptCfg opt_;
+  int col_off1_ = 0, B_ = 16, dev_ = 0, clock_khz_ = 100000;
+  double p1_ = 0, p2_ = 0, timeout_s_ = 30.0;
   sl::IpcAllReduce* ipc_ = nullptr;
   sl::HyArgs a_{};
   bool ok_ = false;

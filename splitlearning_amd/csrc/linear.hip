@@ -21,6 +21,7 @@
 //   Variants that measured slower (non-temporal loads, software-pipelined forward,
 //   row-blocked and loads-first wgrad) were removed after measurement (docs/PERF.md).
 #include "common.h"
+#include "kernels.h"
 
 #include <algorithm>
 
@@ -31,9 +32,6 @@ int g_bf16 = 0;
 int g_nn_splits = 0;
 int g_nn_wm = 0;
 int g_nt_splits = 0;
-
-hipError_t gemm_nt(const float* X, int ldx, const float* W, int ldw, float* Y, int ldy, int M, int N, int K, Epi e,
-                   bool bf16, float* ws, int64_t ws_elems, hipStream_t st);
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -706,28 +704,6 @@ hipError_t linear_fwd_partial(const float* X, int ldx, const float* W, int ldw, 
     skinny_fwd_kernel<4, 4, false><<<g3, 256, 0, st>>>(X, ldx, W, ldw, ws, N, M, N, K, e, ws, slab);
   else
     skinny_fwd_kernel<2, 4, false><<<g3, 128, 0, st>>>(X, ldx, W, ldw, ws, N, M, N, K, e, ws, slab);
-  *S_out = S;
-  return hipGetLastError();
-}
-
-hipError_t linear_dgrad_partial(const float* dZ, int ldz, const float* W, int ldw, int M, int N, int K, float* ws,
-                                int64_t ws_elems, int* S_out, hipStream_t st) {
-  *S_out = 1;
-  if (M <= 0 || K <= 0) return hipSuccess;
-  const int kt = (K + 63) / 64, mt = (M + 15) / 16;
-  int S = 1;
-  while (S < 16 && kt * mt * S < 768 && N / (S * 2) >= 64) S *= 2;
-  const int64_t slab = (int64_t)M * K;
-  if (ws_elems < slab * S) S = 1;
-  if (ws_elems < slab) return hipErrorInvalidValue;
-  dim3 grid(kt, mt, S);
-  if (g_bf16)
-    skinny_dgrad_kernel<8, true><<<grid, 512, 0, st>>>(dZ, ldz, W, ldw, nullptr, 0, 1.f, ws, S == 1 ? K : 0,
-                                                        S == 1 ? 0 : slab, M, N, K);
-  else if (S == 1)
-    skinny_dgrad_kernel<8><<<grid, 512, 0, st>>>(dZ, ldz, W, ldw, nullptr, 0, 1.f, ws, K, 0, M, N, K);
-  else
-    skinny_dgrad_kernel<8><<<grid, 512, 0, st>>>(dZ, ldz, W, ldw, nullptr, 0, 1.f, ws, 0, slab, M, N, K);
   *S_out = S;
   return hipGetLastError();
 }

@@ -8,6 +8,7 @@
 // SURVEY §2.7 K9, K10.  One wave64 per row; all reductions are in-register
 // shuffles, no LDS.
 #include "common.h"
+#include "kernels.h"
 
 namespace sl {
 

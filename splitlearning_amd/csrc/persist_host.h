@@ -10,10 +10,18 @@
 #include <cstdint>
 #include <vector>
 
+#include "args.h"
 #include "host.h"
+#include "resident.h"
 
 namespace sl {
 namespace host {
+
+// a tail layer's parameters and optimizer state as the kernels take them (v / vb null without Adam)
+inline ResLayer res_layer(const args::TailLayer& L) {
+  return ResLayer{L.W.data_ptr<float>(), L.s0.data_ptr<float>(), L.v(),
+                  L.b.data_ptr<float>(), L.sb0.data_ptr<float>(), L.vb()};
+}
 
 inline at::Tensor upload(const std::vector<float>& v, const at::Device& dev) {
   return at::from_blob(const_cast<float*>(v.data()), {(int64_t)v.size()}, at::TensorOptions().dtype(at::kFloat)).to(dev);

@@ -37,7 +37,6 @@
 // alone on the main stream, measured slower: 87-88 k vs 92-94 k samples/s at vanilla ws = 2,
 // profiles/r3_vanilla_side_stream_ab.txt.)
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
 
 #include <rccl/rccl.h>
 
@@ -46,33 +45,13 @@
 #include <tuple>
 #include <vector>
 
+#include "args.h"
 #include "comm.h"
 #include "common.h"
 #include "fused.h"
 #include "host.h"
+#include "kernels.h"
 #include "ipc_p2p.h"
-
-namespace sl {
-hipError_t conv_fwd(const void* x, bool x_u8, const int64_t* idx, int64_t row0, int B, const float* w,
-                    const float* b, float* y, uint8_t* am, hipStream_t st, const int64_t* lab_in,
-                    int64_t* lab_out, const ConvPending* pend);
-hipError_t conv_bwd_step(const float* dy, const float* y, const uint8_t* am, const void* x, bool x_u8,
-                         const int64_t* idx, int B, float* w, float* b, float* slab, float* s0w, float* s1w,
-                         float* s0b, float* s1b, SlOpt o, hipStream_t st, bool defer, const ConvPending* pend);
-hipError_t conv_apply(const ConvPending& p, float* w, float* b, hipStream_t st);
-hipError_t head_step(const float* X, float* W, float* b, const int64_t* y, int64_t ignore, float scale,
-                     float* loss_rows, float* dX, float* s0w, float* s1w, float* s0b, float* s1b, int M, int K, int C,
-                     SlOpt o, bool mask_dx, hipStream_t st);
-hipError_t linear_fwd(const float* X, int ldx, const float* W, int ldw, float* Y, int ldy, int M, int N, int K,
-                      Epi e, float* ws, int64_t ws_elems, hipStream_t st);
-hipError_t linear_dgrad(const float* dZ, int ldz, const float* W, int ldw, const float* hprev, int ldh,
-                        float scale, float* dX, int ldx, float* ws, int64_t ws_elems, int M, int N, int K,
-                        hipStream_t st);
-hipError_t linear_epilogue(const float* P, int ldp, float* Y, int ldy, int M, int N, Epi e, int S, int64_t slab,
-                           hipStream_t st);
-hipError_t linear_fwd_partial(const float* X, int ldx, const float* W, int ldw, int M, int N, int K, float* ws,
-                              int64_t ws_elems, int max_split, int* S_out, hipStream_t st);
-}  // namespace sl
 
 namespace py = pybind11;
 
@@ -80,12 +59,11 @@ namespace {
 
 constexpr int kCut = 5408;
 
-void ck(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e)); }
+using sl::args::ck;
 
-at::Tensor get(const py::dict& d, const char* k) {
-  TORCH_CHECK(d.contains(k), "SplitEpoch: missing '", k, "'");
-  return d[k].cast<at::Tensor>();
-}
+using sl::args::cur_stream;
+using sl::args::dict_tensor;
+constexpr const char* kWho = "SplitEpoch";
 
 float* opt_ptr(const py::dict& d, const char* k) {
   if (!d.contains(k) || d[k].is_none()) return nullptr;
@@ -93,28 +71,11 @@ float* opt_ptr(const py::dict& d, const char* k) {
 }
 
 void need(const at::Tensor& t, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), "SplitEpoch: ", what,
-              " must be a contiguous f32 GPU tensor");
+  TORCH_CHECK(sl::args::dense_f32(t), "SplitEpoch: ", what, " must be a contiguous f32 GPU tensor");
 }
 
-struct Opt {
-  int kind = 1;
-  double lr = 0, beta1 = 0, beta2 = 0, eps = 0, wd = 0, mom = 0;
-  SlOpt at(int64_t t) const { return sl::make_opt_raw(kind, lr, beta1, beta2, eps, wd, mom, t, nullptr); }
-};
-
-Opt read_opt(const py::dict& d) {
-  Opt o;
-  o.kind = d["kind"].cast<int>();
-  TORCH_CHECK(o.kind == 1 || o.kind == 2, "SGD-momentum or Adam");
-  o.lr = d["lr"].cast<double>();
-  o.beta1 = d["beta1"].cast<double>();
-  o.beta2 = d["beta2"].cast<double>();
-  o.eps = d["eps"].cast<double>();
-  o.wd = d["wd"].cast<double>();
-  o.mom = d["momentum"].cast<double>();
-  return o;
-}
+using Opt = sl::args::OptCfg;
+using sl::args::read_opt;
 
 // A parameter tensor and its optimizer state (s1 = Adam's v, null for SGD)
 struct Param {
@@ -126,7 +87,7 @@ struct Param {
 Param read_param(const py::dict& d, const char* name) {
   const py::dict e = d[name].cast<py::dict>();
   Param q;
-  q.p = get(e, "p");
+  q.p = dict_tensor(e, "p", kWho);
   need(q.p, name);
   q.s0 = opt_ptr(e, "s0");
   q.s1 = opt_ptr(e, "s1");
@@ -195,8 +156,8 @@ class SplitEpoch {
     }
     at::Device dev = at::kCPU;
     if (alice) {
-      x_ = get(cfg, "x");
-      y_ = get(cfg, "y");
+      x_ = dict_tensor(cfg, "x", kWho);
+      y_ = dict_tensor(cfg, "y", kWho);
       TORCH_CHECK(x_.is_cuda() && x_.scalar_type() == at::kByte && x_.is_contiguous() && x_.numel() % 784 == 0,
                   "shard pixels uint8 [N, 784]");
       TORCH_CHECK(y_.is_cuda() && y_.scalar_type() == at::kLong && y_.is_contiguous() &&
@@ -265,7 +226,7 @@ class SplitEpoch {
     // split factor is the Python path's), at least that path's minimum sizes
     auto ws = [&](const char* k, int64_t n) {
       if (!cfg.contains(k)) return f32(n);
-      at::Tensor t = get(cfg, k);
+      at::Tensor t = dict_tensor(cfg, k, kWho);
       need(t, k);
       TORCH_CHECK(t.numel() >= n, "SplitEpoch: workspace '", k, "' too small");
       return t;
@@ -286,7 +247,7 @@ class SplitEpoch {
     TORCH_CHECK(role_ == 0, "SplitEpoch.run: both sides in this process (role 0)");
     const int64_t n = check_order(order);
     if (n == 0) return py::make_tuple(t_a, t_b, fwd_count);
-    const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    const hipStream_t st = cur_stream();
     const int64_t* ord = order.data_ptr<int64_t>();
     const int64_t T = (n + B_ - 1) / B_;
     auto rows = [&](int64_t i) { return (int)std::min<int64_t>(B_, n - i * B_); };
@@ -326,7 +287,7 @@ class SplitEpoch {
     TORCH_CHECK(role_ == 1, "SplitEpoch.run_alice: the Alice's side of a remote placement (role 1)");
     const int64_t n = check_order(order);
     if (n == 0) return t_a;
-    const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    const hipStream_t st = cur_stream();
     const int64_t* ord = order.data_ptr<int64_t>();
     const int64_t T = (n + B_ - 1) / B_;
     auto rows = [&](int64_t i) { return (int)std::min<int64_t>(B_, n - i * B_); };
@@ -371,7 +332,7 @@ class SplitEpoch {
   py::tuple run_bob(int64_t n, int64_t t_b, int64_t fwd_count, int64_t seed_base) {
     TORCH_CHECK(role_ == 2, "SplitEpoch.run_bob: Bob's side of a remote placement (role 2)");
     if (n <= 0) return py::make_tuple(t_b, fwd_count);
-    const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    const hipStream_t st = cur_stream();
     const int64_t T = (n + B_ - 1) / B_;
     const int N1 = (int)L_[0].w.p.size(0), N2 = (int)L_[1].w.p.size(0);
     float* act = act_[0].data_ptr<float>();

@@ -11,7 +11,6 @@
 // of her epoch as one launch exchanging run_bob's four messages per step on the peer-mapped channel
 // itself (csrc/ushape.hip REM); her side stays csrc/split.cpp run_alice.
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
 
 #include <string>
 #include <tuple>
@@ -25,10 +24,9 @@ namespace py = pybind11;
 
 namespace {
 
-at::Tensor us_get(const py::dict& d, const char* k) {
-  TORCH_CHECK(d.contains(k) && !d[k].is_none(), "UShapeEpoch: missing '", k, "'");
-  at::Tensor t = d[k].cast<at::Tensor>();
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), "UShapeEpoch: '", k, "' f32 GPU");
+at::Tensor param(const py::dict& d, const char* k) {
+  at::Tensor t = sl::args::dict_tensor(d, k, "UShapeEpoch");
+  TORCH_CHECK(sl::args::dense_f32(t), "UShapeEpoch: '", k, "' f32 GPU");
   return t;
 }
 
@@ -37,7 +35,7 @@ struct Six {
 };
 
 Six us_six(const py::dict& d) {
-  Six s{us_get(d, "W"), us_get(d, "m"), us_get(d, "v"), us_get(d, "b"), us_get(d, "mb"), us_get(d, "vb")};
+  Six s{param(d, "W"), param(d, "m"), param(d, "v"), param(d, "b"), param(d, "mb"), param(d, "vb")};
   TORCH_CHECK(s.m.sizes() == s.W.sizes() && s.v.sizes() == s.W.sizes() && s.mb.numel() == s.b.numel() &&
                   s.vb.numel() == s.b.numel(),
               "UShapeEpoch: parameter / moment shapes");
@@ -84,9 +82,9 @@ class UShapeEpoch {
     timeout_s_ = cfg.contains("timeout_s") ? cfg["timeout_s"].cast<double>() : 30.0;
     const int wg = cfg.contains("workgroups") ? cfg["workgroups"].cast<int>() : 0;
     dev_ = f1_.W.device().index();
-    int cus = 0, khz = 0;
+    int cus = 0;
     TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_) == hipSuccess, "CU count");
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev_) != hipSuccess || khz <= 0) khz = 100000;
+    const int khz = sl::args::clock_khz(dev_);
 
     sl::UsArgs& a = a_;
     a = sl::UsArgs{};
@@ -189,7 +187,7 @@ class UShapeEpoch {
     sl::host::fill_adam(tabf, 8, 2, t_a, [&](int64_t step) { return us_opt(ao_, step); });
     sl::host::fill_rows(tabf, 8, 4, 5, [&](int64_t i) { return std::min<int64_t>(B_, n - i * B_); });
     tabf_ = sl::host::upload(tabf, dev);
-    const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    const hipStream_t st = sl::args::cur_stream();
     const int e = sl::host::run_chunks("U-shape", a_.err, err_, st, S, max_steps_, fault_step_,
                                           [&](int64_t s0, int64_t ns, int fault) {
       sl::UsArgs a = a_;
@@ -221,7 +219,7 @@ class UShapeEpoch {
     sl::host::fill_adam(tabf, 8, 0, t_b, [&](int64_t step) { return us_opt(bo_, step); });
     sl::host::fill_rows(tabf, 8, 4, 5, rows_at);
     tabf_ = sl::host::upload(tabf, dev);
-    const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    const hipStream_t st = sl::args::cur_stream();
     const int64_t N2 = a_.N2, cut = (int64_t)sl::kUsCh * sl::kUsP;
     log_.clear();
     const int e = sl::host::run_chunks("U-shape", a_.err, err_, st, S, max_steps_, fault_step_,

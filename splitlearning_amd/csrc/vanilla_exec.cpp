@@ -12,7 +12,6 @@
 // messages on the peer-mapped channel itself (csrc/vanilla.hip REM); her side stays
 // csrc/split.cpp run_alice, so the per-batch run_bob is the drop-in fallback.
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
 
 #include <cstdlib>
 #include <string>
@@ -27,14 +26,8 @@ namespace py = pybind11;
 
 namespace {
 
-at::Tensor va_get(const py::dict& d, const char* k) {
-  TORCH_CHECK(d.contains(k) && !d[k].is_none(), "VanillaEpoch: missing '", k, "'");
-  return d[k].cast<at::Tensor>();
-}
-
-void va_f32(const at::Tensor& t, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), "VanillaEpoch: ", what, " f32 GPU");
-}
+using sl::args::dict_tensor;
+constexpr const char* kWho = "VanillaEpoch";
 
 class VanillaEpoch {
  public:
@@ -44,20 +37,12 @@ class VanillaEpoch {
   // workgroups (0: cooperative launch of 256).  Remote Alice: channel (an open IpcChannel) and
   // peer (her rank) in place of alice / x / y; G workgroups (default 256)
   explicit VanillaEpoch(const py::dict& cfg) {
-    auto layers = cfg["layers"].cast<std::vector<py::dict>>();
-    TORCH_CHECK(layers.size() == 3, "VanillaEpoch drives model2_sisa's 3 layers");
-    for (int i = 0; i < 3; ++i) {
-      const py::dict& d = layers[i];
-      W_[i] = va_get(d, "W");
-      b_[i] = va_get(d, "b");
-      s0_[i] = va_get(d, "s0");
-      sb0_[i] = va_get(d, "sb0");
-      for (const at::Tensor* t : {&W_[i], &b_[i], &s0_[i], &sb0_[i]}) va_f32(*t, "layer tensors");
-      TORCH_CHECK(W_[i].dim() == 2 && s0_[i].sizes() == W_[i].sizes() && b_[i].numel() == W_[i].size(0) &&
-                      sb0_[i].numel() == W_[i].size(0),
-                  "layer shapes");
+    L_ = sl::args::read_tail_layers(cfg, kWho);
+    // SGD-momentum only: no second moments, whatever the dicts hold
+    for (auto& L : L_) {
+      TORCH_CHECK(L.sb0.numel() == L.N, "VanillaEpoch: layer shapes");
+      L.s1 = L.sb1 = at::Tensor();
     }
-    TORCH_CHECK(W_[1].size(1) == W_[0].size(0) && W_[2].size(1) == W_[1].size(0), "layer chain shapes");
     rem_ = cfg.contains("channel") && !cfg["channel"].is_none();
     if (rem_) {
       const py::object ch = cfg["channel"];
@@ -69,15 +54,16 @@ class VanillaEpoch {
                   "VanillaEpoch: an open channel and the Alice's rank");
     } else {
       py::dict al = cfg["alice"].cast<py::dict>();
-      cw_ = va_get(al, "w");
-      cb_ = va_get(al, "b");
-      cmw_ = va_get(al, "s0w");
-      cmb_ = va_get(al, "s0b");
-      for (const at::Tensor* t : {&cw_, &cb_, &cmw_, &cmb_}) va_f32(*t, "conv tensors");
+      cw_ = dict_tensor(al, "w", kWho);
+      cb_ = dict_tensor(al, "b", kWho);
+      cmw_ = dict_tensor(al, "s0w", kWho);
+      cmb_ = dict_tensor(al, "s0b", kWho);
+      for (const at::Tensor* t : {&cw_, &cb_, &cmw_, &cmb_})
+        TORCH_CHECK(sl::args::dense_f32(*t), "VanillaEpoch: conv tensors f32 GPU");
       TORCH_CHECK(cw_.numel() == 288 && cb_.numel() == 32 && cmw_.numel() == 288 && cmb_.numel() == 32,
                   "conv 32 x 1 x 3 x 3");
-      x_ = va_get(cfg, "x");
-      y_ = va_get(cfg, "y");
+      x_ = dict_tensor(cfg, "x", kWho);
+      y_ = dict_tensor(cfg, "y", kWho);
       TORCH_CHECK(x_.is_cuda() && x_.scalar_type() == at::kByte && x_.is_contiguous() && x_.numel() % 784 == 0,
                   "shard pixels uint8 [N, 784]");
       TORCH_CHECK(y_.is_cuda() && y_.scalar_type() == at::kLong && y_.numel() * 784 == x_.numel(), "labels int64 [N]");
@@ -86,18 +72,17 @@ class VanillaEpoch {
     const double p1 = cfg["p1"].cast<double>(), p2 = cfg["p2"].cast<double>();
     timeout_s_ = cfg.contains("timeout_s") ? cfg["timeout_s"].cast<double>() : 30.0;
 
-    dev_ = W_[0].device().index();
+    dev_ = L_[0].W.device().index();
     int cus = 0;
     TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_) == hipSuccess, "CU count");
-    int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev_) != hipSuccess || khz <= 0) khz = 100000;
+    const int khz = sl::args::clock_khz(dev_);
 
     sl::VaArgs& a = a_;
     a = sl::VaArgs{};
-    a.N1 = (int)W_[0].size(0);
-    a.K1 = (int)W_[0].size(1);
-    a.N2 = (int)W_[1].size(0);
-    a.C = (int)W_[2].size(0);
+    a.N1 = (int)L_[0].W.size(0);
+    a.K1 = (int)L_[0].W.size(1);
+    a.N2 = (int)L_[1].W.size(0);
+    a.C = (int)L_[2].W.size(0);
     a.C4 = (a.C + 3) & ~3;
     a.M = B_;
     a.G = rem_ && cfg.contains("G") ? cfg["G"].cast<int>() : sl::kVaG;
@@ -131,7 +116,7 @@ class VanillaEpoch {
     if (why_.empty()) why_ = sl::vanilla_check(a);
     if (why_.empty()) why_ = tables();
     if (why_.empty()) {
-      auto opt = at::TensorOptions().dtype(at::kFloat).device(W_[0].device());
+      auto opt = at::TensorOptions().dtype(at::kFloat).device(L_[0].W.device());
       int64_t off = 0;
       auto take = [&](int64_t n) {
         const int64_t o = off;
@@ -159,23 +144,15 @@ class VanillaEpoch {
         if (w < a.HW) ++sn[3 * 8 + (w & 7)];   // Z: head workgroups
         ++sn[4 * 8 + (w & 7)];                 // X: every conv job
       }
-      shard_n_ = at::tensor(sn, at::TensorOptions().dtype(at::kInt)).to(W_[0].device());
+      shard_n_ = at::tensor(sn, at::TensorOptions().dtype(at::kInt)).to(L_[0].W.device());
       a.cnt = reinterpret_cast<unsigned*>(cnt_.data_ptr<int>());
       a.shard_n = shard_n_.data_ptr<int>();
       a.err = err_.data_ptr<int>();
       a.tab = tab_.data_ptr<int>();
       a.timeout = (int64_t)(timeout_s_ * 1000.0 * khz);
-      auto setL = [&](sl::ResLayer& r, int i) {
-        r.W = W_[i].data_ptr<float>();
-        r.b = b_[i].data_ptr<float>();
-        r.m = s0_[i].data_ptr<float>();
-        r.mb = sb0_[i].data_ptr<float>();
-        r.v = nullptr;
-        r.vb = nullptr;
-      };
-      setL(a.L1, 0);
-      setL(a.L2, 1);
-      setL(a.L3, 2);
+      a.L1 = sl::host::res_layer(L_[0]);
+      a.L2 = sl::host::res_layer(L_[1]);
+      a.L3 = sl::host::res_layer(L_[2]);
       if (!rem_) {
         a.img = x_.data_ptr<uint8_t>();
         a.cw = cw_.data_ptr<float>();
@@ -226,7 +203,7 @@ class VanillaEpoch {
     TORCH_CHECK(rem_, "VanillaEpoch.run_remote: configured with a channel and peer");
     const int64_t S = n > 0 ? (n + B_ - 1) / B_ : 0;
     if (S == 0) return py::make_tuple(t_b, fwd_count);
-    epoch(n, S, loss_rows, fwd_count, seed_base, trace_all, trace_step, W_[0].device());
+    epoch(n, S, loss_rows, fwd_count, seed_base, trace_all, trace_step, L_[0].W.device());
     return py::make_tuple(t_b + S, fwd_count + S);
   }
 
@@ -256,7 +233,7 @@ class VanillaEpoch {
     sl::host::fill_rows(tabf, 4, 2, 0, rows_at);
     tabf_ = sl::host::upload(tabf, dev);
     seeds_ = sl::host::step_seeds(S, seed_base, fwd_count, dev);
-    const hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    const hipStream_t st = sl::args::cur_stream();
     // launches of at most kVaMaxS steps (one launch of S steps is bitwise S one-step launches)
     const int64_t cs = std::min<int64_t>(S, max_steps_);
     xr_ = at::empty({cs * 16 * a_.K1}, at::TensorOptions().dtype(at::kFloat).device(dev));
@@ -398,11 +375,11 @@ class VanillaEpoch {
       const std::string e = fill();
       if (!e.empty()) return e;
     }
-    tab_ = at::tensor(tab, at::TensorOptions().dtype(at::kInt)).to(W_[0].device());
+    tab_ = at::tensor(tab, at::TensorOptions().dtype(at::kInt)).to(L_[0].W.device());
     return "";
   }
 
-  at::Tensor W_[3], b_[3], s0_[3], sb0_[3];
+  std::array<sl::args::TailLayer, 3> L_;
   at::Tensor cw_, cb_, cmw_, cmb_, x_, y_;
   int B_ = 16, dev_ = 0;
   int64_t fault_step_ = -1;
