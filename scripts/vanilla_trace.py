@@ -45,7 +45,7 @@ def main():
     a1 = s.alices[1]
     order = a1.train.shuffled_order(torch.Generator().manual_seed(1))[:n].to(dev)
     assert order.numel() == n, (order.numel(), n)
-    assert sn.persistent_vanilla_ok(s, 1), s.__dict__.get("split_persist_reason")
+    assert sn.persistent_ok(s, 1, "vanilla"), s.__dict__.get("split_persist_reason")
     ts = []
     for r in range(a.reps + 1):
         torch.cuda.synchronize()
@@ -57,7 +57,7 @@ def main():
     ts.sort()
     print(f"vanilla persistent epoch: {a.batches} steps of B = {a.B}: {ts[len(ts) // 2]:.1f} us/step "
           f"(min {ts[0]:.1f}, max {ts[-1]:.1f})", flush=True)
-    cfg = sn._va_cfg(s, 1)
+    cfg = sn.persist_cfg(s, 1, "vanilla")
     ex = s.ops.C().VanillaEpoch(cfg)
     G, T = 256, 8
     tall = torch.zeros((T, G, 16), dtype=torch.int64, device=dev)

@@ -6,10 +6,13 @@ with `--bob_tp 1`), each side's half of the same loop with the per-batch message
 split channel (csrc/ipc_p2p.h peer-mapped messages, or RCCL).
 
 The executor issues the same launches, with the same arguments, dropout seeds, workspaces
-and optimizer step counts, as `VanillaSession.split_epoch` / `UShapeSession.split_epoch` in
-their look-ahead order, so the parameters it produces are bit-identical to the Python
-loop's (tests/test_split_native_gpu.py); the Python loop
-stays the path for every other placement and for `--python_epoch`.
+and optimizer step counts, as the Python loop of `SplitSession.split_epoch`
+(protocols/split.py) in its look-ahead order, so the parameters it produces are bit-identical
+to that loop's (tests/test_split_native_gpu.py); the Python loop stays the path for every
+other placement and for `--python_epoch`.
+
+The persistent one-launch epochs (`_C.VanillaEpoch`, `_C.UShapeEpoch`) share one gate, one
+cfg per side and one fail-safe runner here; `_Vanilla` / `_UShape` hold what differs.
 
 Reference hot loops: data_entities_vanilla.py:66-76 and data_entities.py:65-81.
 """
@@ -24,9 +27,10 @@ _KIND = {"sgd": 1, "adam": 2}
 SPLIT_MIN_B, SPLIT_MAX_B = 1, 64
 
 
-def _opt(cfg) -> dict:
-    return {"kind": _KIND[cfg.kind], "lr": cfg.lr, "beta1": cfg.beta1, "beta2": cfg.beta2, "eps": cfg.eps,
-            "wd": cfg.weight_decay, "momentum": cfg.momentum}
+def _opt(cfg, adam_only: bool = False) -> dict:
+    """An optimizer's settings as the executors read them (`_C.UShapeEpoch` is Adam only)."""
+    d = {"lr": cfg.lr, "beta1": cfg.beta1, "beta2": cfg.beta2, "eps": cfg.eps, "wd": cfg.weight_decay}
+    return d if adam_only else {"kind": _KIND[cfg.kind], "momentum": cfg.momentum, **d}
 
 
 def _param(slot, name: str, p: torch.Tensor) -> dict:
@@ -99,7 +103,7 @@ def _bob_done(sess, cid: int, t_b: int, fc: int):
 
 def _count(sess, kind: str):
     """Per-session tally of native split epochs by kind (bench.py reports it)."""
-    c = sess.__dict__.setdefault("native_split_epochs", {})
+    c = sess.native_split_epochs
     c[kind] = c.get(kind, 0) + 1
 
 
@@ -123,124 +127,10 @@ def run_native_split_epoch(sess, cid: int, order: torch.Tensor, mode: str):
     return ex
 
 
-# ---------------------------------------------------------------------- persistent vanilla epoch
-def persistent_vanilla_ok(sess, cid: int) -> bool:
-    """Whether `run_persistent_vanilla_epoch` may drive this epoch: the co-located native
-    conditions, fp32 SGD-momentum on both sides, batches of at most 16 rows, the flag, and no
-    earlier failure of the persistent executor in this session."""
-    if getattr(sess.args, "split_persist", "auto") == "off" or sess.__dict__.get("_va_off"):
-        return False
-    if getattr(sess.comm, "host_staging", False):
-        return False   # ranks share this GPU (--ranks_share_gpu): 256 co-resident workgroups are not assured
-    if not native_split_ok(sess, cid, "vanilla") or not hasattr(sess.ops.C(), "VanillaEpoch"):
-        return False
-    # vanilla.hip computes in exact fp32 only: a bf16 run (fp32 master weights, bf16 operands
-    # through the global compute-dtype switch) stays on the per-batch executor, whose kernels
-    # honour it, instead of silently running fp32
-    dt = getattr(sess.args, "dtype", "fp32")
-    C = sess.ops.C()
-    if dt != "fp32" or (hasattr(C, "get_compute_dtype") and C.get_compute_dtype() != "fp32"):
-        sess.__dict__["split_persist_reason"] = f"dtype {dt if dt != 'fp32' else C.get_compute_dtype()}: fp32 only"
-        return False
-    a = sess.alices[cid]
-    if not 1 <= sess.B <= 16:
-        # every product's MFMA row block is the batch (csrc/vanilla.hip): larger batches run per batch
-        sess.__dict__["split_persist_reason"] = f"batch {sess.B} > 16: per-batch executor"
-        return False
-    return (a.slot.cfg.kind == "sgd" and sess.bob_slot(cid).cfg.kind == "sgd"
-            and len(sess.tail.layers) == 3 and all(L.W.dtype == torch.float32 for L in sess.tail.layers))
-
-
-def _va_cfg(sess, cid: int) -> dict:
-    a = sess.alices[cid]
-    a.front.flush()
-    w, b = a.front.params
-    aw, ab = _param(a.slot, "conv.weight", w), _param(a.slot, "conv.bias", b)
-    bslot = sess.bob_slot(cid)
-    layers = []
-    for L in sess.tail.layers:
-        pw, pb = _param(bslot, f"{L.spec.name}.weight", L.W), _param(bslot, f"{L.spec.name}.bias", L.b)
-        layers.append({"W": pw["p"], "b": pb["p"], "s0": pw["s0"], "sb0": pb["s0"]})
-    bo, ao = bslot.cfg, a.slot.cfg
-    return {"layers": layers, "lr": bo.lr, "momentum": bo.momentum, "wd": bo.weight_decay,
-            "alice": {"w": aw["p"], "b": ab["p"], "s0w": aw["s0"], "s0b": ab["s0"]},
-            "alice_lr": ao.lr, "alice_momentum": ao.momentum, "alice_wd": ao.weight_decay,
-            "x": a.train.x, "y": a.train.y, "B": sess.B,
-            "p1": sess.tail.layers[0].spec.dropout, "p2": sess.tail.layers[1].spec.dropout,
-            "timeout_s": float(getattr(sess.args, "persist_timeout_s", 30.0)),
-            # a plain (non-cooperative) launch of the same grid for rocprofv3, whose process dies at
-            # exit after any cooperative launch (docs/PERF.md, tools/coop_repro.hip)
-            "workgroups": int(os.environ.get("SL_PERSIST_WORKGROUPS", "0"))}
-
-
-def run_persistent_vanilla_epoch(sess, cid: int, order: torch.Tensor) -> bool:
-    """One vanilla epoch of a co-located Alice_cid as ONE launch (`_C.VanillaEpoch`,
-    csrc/vanilla.hip).  Fail-safe: the Alice's and Bob's parameters and momentum buffers are
-    copied first; if the launch fails they are restored, the persistent executor is switched
-    off for the session (`split_persist_fallback`) and False is returned, so the caller runs
-    the epoch on the per-batch executor instead."""
-    cfg = _va_cfg(sess, cid)
-    ex = sess.ops.C().VanillaEpoch(cfg)
-    if not ex.ok():
-        sess.__dict__["_va_off"] = True
-        sess.__dict__["split_persist_reason"] = ex.why()
-        return False
-    a = sess.alices[cid]
-    order = order.to(sess.device, torch.int64).contiguous()
-    state = [L["W"] for L in cfg["layers"]] + [L["b"] for L in cfg["layers"]]
-    state += [L["s0"] for L in cfg["layers"]] + [L["sb0"] for L in cfg["layers"]] + list(cfg["alice"].values())
-    snap = [t.clone() for t in state] if getattr(sess.args, "persistent_failsafe", "on") != "off" else None
-    B = sess.B
-    nb = -(-int(order.numel()) // B)
-    loss = torch.empty(max(nb, 1) * B, dtype=torch.float32, device=sess.device)
-    sess.tail._pre = None
-    if sess.__dict__.get("_va_max_steps"):
-        ex.set_max_steps(int(sess._va_max_steps))      # tests: the epoch as several launches
-    fault = sess.__dict__.pop("_va_fault_step", None)
-    if fault is not None:
-        ex.set_fault_step(int(fault))
-    try:
-        t_a, t_b, fc = ex.run(order, loss, a.slot.t, sess.bob_slot(cid).t, sess.tail.fwd_count, sess.tail.seed_base)
-    except RuntimeError as e:
-        if snap is None:
-            raise
-        for t, s in zip(state, snap):
-            t.copy_(s)
-        sess.__dict__["_va_off"] = True
-        sess.__dict__["split_persist_fallback"] = str(e).splitlines()[0][:200]
-        return False
-    _count(sess, "persistent")
-    a.slot.t = int(t_a)
-    _bob_done(sess, cid, t_b, fc)
-    sess.__dict__["last_split_losses"] = loss[:order.numel()]
-    return True
-
-
-# ---------------------------------------------------------------------- persistent U-shape epoch
-def persistent_ushape_ok(sess, cid: int) -> bool:
-    """Whether `run_persistent_ushape_epoch` may drive this epoch: the co-located native
-    conditions, Adam on both sides, fp32 or bf16 compute (as --dtype), batches of at most 16 rows, the flag, and no
-    earlier failure of the persistent executor in this session."""
-    if getattr(sess.args, "split_persist", "auto") == "off" or sess.__dict__.get("_us_off"):
-        return False
-    if getattr(sess.comm, "host_staging", False):
-        return False   # ranks share this GPU (--ranks_share_gpu): 256 co-resident workgroups are not assured
-    if not native_split_ok(sess, cid, "ushape") or not hasattr(sess.ops.C(), "UShapeEpoch"):
-        return False
-    dt = getattr(sess.args, "dtype", "fp32")
-    C = sess.ops.C()
-    cdt = C.get_compute_dtype() if hasattr(C, "get_compute_dtype") else "fp32"
-    if dt not in ("fp32", "bf16") or cdt != dt:
-        # bf16 runs the kernel's bf16 instantiation (bf16 operands, fp32 state), but only when the
-        # compute dtype the per-batch kernels use agrees with --dtype
-        sess.__dict__["split_persist_reason"] = f"dtype {dt} with compute dtype {cdt}"
-        return False
-    a = sess.alices[cid]
-    if not 1 <= sess.B <= 16:
-        sess.__dict__["split_persist_reason"] = f"batch {sess.B} > 16: per-batch executor"
-        return False
-    return (a.slot.cfg.kind == "adam" and sess.bob_slot(cid).cfg.kind == "adam"
-            and len(sess.tail.layers) == 2 and all(L.W.dtype == torch.float32 for L in sess.tail.layers))
+# ---------------------------------------------------------------------- persistent epochs
+def _rows(slot, L) -> dict:
+    pw, pb = _param(slot, f"{L.spec.name}.weight", L.W), _param(slot, f"{L.spec.name}.bias", L.b)
+    return {"W": pw["p"], "b": pb["p"], "s0": pw["s0"], "sb0": pb["s0"]}
 
 
 def _six(slot, name: str, W: torch.Tensor, b: torch.Tensor) -> dict:
@@ -248,66 +138,182 @@ def _six(slot, name: str, W: torch.Tensor, b: torch.Tensor) -> dict:
     return {"W": W, "m": sw["m"], "v": sw["v"], "b": b, "mb": sb["m"], "vb": sb["v"]}
 
 
-def _adam(cfg) -> dict:
-    return {"lr": cfg.lr, "beta1": cfg.beta1, "beta2": cfg.beta2, "eps": cfg.eps, "wd": cfg.weight_decay}
+def _loss_buf(sess, nb: int) -> torch.Tensor:
+    return torch.empty(max(nb, 1) * sess.B, dtype=torch.float32, device=sess.device)
 
 
-def _us_cfg(sess, cid: int) -> dict:
-    a = sess.alices[cid]
-    a.front.flush()
-    w, b = a.front.params
-    H = a.head.layers[0]
-    bslot = sess.bob_slot(cid)
-    L1, L2 = sess.tail.layers
-    return {"fc1": _six(bslot, L1.spec.name, L1.W, L1.b), "fc2": _six(bslot, L2.spec.name, L2.W, L2.b),
-            "conv": _six(a.slot, "front.conv", w, b), "head": _six(a.slot, f"head.{H.spec.name}", H.W, H.b),
-            "bob_opt": _adam(bslot.cfg), "alice_opt": _adam(a.slot.cfg),
-            "x": a.train.x, "y": a.train.y, "B": sess.B,
-            "timeout_s": float(getattr(sess.args, "persist_timeout_s", 30.0)),
-            "workgroups": int(os.environ.get("SL_PERSIST_WORKGROUPS", "0")),
-            "bf16": getattr(sess.args, "dtype", "fp32") == "bf16"}
+class _Vanilla:
+    """`_C.VanillaEpoch` (csrc/vanilla.hip): fp32 SGD-momentum, three tail layers."""
+    executor, opt_kind, n_layers, remote_env = "VanillaEpoch", "sgd", 3, "SL_VA_REMOTE_G"
+
+    @staticmethod
+    def dtype_reason(dt: str, cdt: str):
+        # vanilla.hip computes in exact fp32 only: a bf16 run (fp32 master weights, bf16 operands
+        # through the global compute-dtype switch) stays on the per-batch executor, whose kernels
+        # honour it, instead of silently running fp32
+        return None if dt == cdt == "fp32" else f"dtype {dt if dt != 'fp32' else cdt}: fp32 only"
+
+    @staticmethod
+    def bob_cfg(sess, cid: int) -> dict:
+        bslot, tail = sess.bob_slot(cid), sess.tail
+        bo = bslot.cfg
+        return {"layers": [_rows(bslot, L) for L in tail.layers], "lr": bo.lr, "momentum": bo.momentum,
+                "wd": bo.weight_decay, "p1": tail.layers[0].spec.dropout, "p2": tail.layers[1].spec.dropout}
+
+    @staticmethod
+    def alice_cfg(sess, cid: int) -> dict:
+        a = sess.alices[cid]
+        a.front.flush()
+        w, b = a.front.params
+        aw, ab, ao = _param(a.slot, "conv.weight", w), _param(a.slot, "conv.bias", b), a.slot.cfg
+        return {"alice": {"w": aw["p"], "b": ab["p"], "s0w": aw["s0"], "s0b": ab["s0"]},
+                "alice_lr": ao.lr, "alice_momentum": ao.momentum, "alice_wd": ao.weight_decay,
+                "x": a.train.x, "y": a.train.y}
+
+    @staticmethod
+    def state(cfg: dict) -> list:
+        """Everything the launch writes: what the fail-safe copies and restores."""
+        return [t for g in cfg["layers"] + [cfg["alice"]] for t in g.values()]
+
+    @staticmethod
+    def run(ex, sess, cid: int, order, loss, nb: int):
+        tail = sess.tail
+        return ex.run(order, loss, sess.alices[cid].slot.t, sess.bob_slot(cid).t, tail.fwd_count, tail.seed_base)
+
+    @staticmethod
+    def run_remote(ex, sess, cid: int, n: int, nb: int):
+        loss, tail = _loss_buf(sess, nb), sess.tail
+        t_b, fc = ex.run_remote(n, loss, sess.bob_slot(cid).t, tail.fwd_count, tail.seed_base)
+        return t_b, fc, loss
 
 
-def run_persistent_ushape_epoch(sess, cid: int, order: torch.Tensor) -> bool:
-    """One U-shape epoch of a co-located Alice_cid as ONE launch (`_C.UShapeEpoch`,
-    csrc/ushape.hip: every parameter and Adam moment of model1 / model2 / model3 on-chip).
-    Fail-safe as `run_persistent_vanilla_epoch`: parameters and moments are copied first; a
-    failed launch restores them, switches the persistent executor off for the session
-    (`split_persist_fallback`) and returns False, so the caller runs the epoch per batch."""
-    cfg = _us_cfg(sess, cid)
-    ex = sess.ops.C().UShapeEpoch(cfg)
+class _UShape:
+    """`_C.UShapeEpoch` (csrc/ushape.hip): Adam, two tail layers, fp32 or bf16 compute as --dtype;
+    it draws no dropout seeds, so the host advances `fwd_count` by the batches run."""
+    executor, opt_kind, n_layers, remote_env = "UShapeEpoch", "adam", 2, "SL_US_REMOTE_G"
+
+    @staticmethod
+    def dtype_reason(dt: str, cdt: str):
+        # bf16 runs the kernel's bf16 instantiation (bf16 operands, fp32 state), but only when the
+        # compute dtype the per-batch kernels use agrees with --dtype
+        return None if dt in ("fp32", "bf16") and cdt == dt else f"dtype {dt} with compute dtype {cdt}"
+
+    @staticmethod
+    def bob_cfg(sess, cid: int) -> dict:
+        bslot = sess.bob_slot(cid)
+        L1, L2 = sess.tail.layers
+        return {"fc1": _six(bslot, L1.spec.name, L1.W, L1.b), "fc2": _six(bslot, L2.spec.name, L2.W, L2.b),
+                "bob_opt": _opt(bslot.cfg, adam_only=True), "bf16": getattr(sess.args, "dtype", "fp32") == "bf16"}
+
+    @staticmethod
+    def alice_cfg(sess, cid: int) -> dict:
+        a = sess.alices[cid]
+        a.front.flush()
+        w, b = a.front.params
+        H = a.head.layers[0]
+        return {"conv": _six(a.slot, "front.conv", w, b), "head": _six(a.slot, f"head.{H.spec.name}", H.W, H.b),
+                "alice_opt": _opt(a.slot.cfg, adam_only=True), "x": a.train.x, "y": a.train.y}
+
+    @staticmethod
+    def state(cfg: dict) -> list:
+        return [t for k in ("fc1", "fc2", "conv", "head") for t in cfg[k].values()]
+
+    @staticmethod
+    def run(ex, sess, cid: int, order, loss, nb: int):
+        t_a, t_b = ex.run(order, loss, sess.alices[cid].slot.t, sess.bob_slot(cid).t)
+        return t_a, t_b, sess.tail.fwd_count + nb
+
+    @staticmethod
+    def run_remote(ex, sess, cid: int, n: int, nb: int):
+        return ex.run_remote(n, sess.bob_slot(cid).t), sess.tail.fwd_count + nb, None
+
+
+_MODES = {"vanilla": _Vanilla, "ushape": _UShape}
+
+
+def _dtypes(sess):
+    C = sess.ops.C()
+    return getattr(sess.args, "dtype", "fp32"), C.get_compute_dtype() if hasattr(C, "get_compute_dtype") else "fp32"
+
+
+def persistent_ok(sess, cid: int, mode: str) -> bool:
+    """Whether `run_persistent_epoch` may drive this epoch: the co-located native conditions,
+    the mode's optimizer on both sides and its compute dtype, batches of at most 16 rows, the
+    flag, and no earlier failure of the persistent executor in this session."""
+    m = _MODES[mode]
+    if getattr(sess.args, "split_persist", "auto") == "off" or sess.persist_off:
+        return False
+    if getattr(sess.comm, "host_staging", False):
+        return False   # ranks share this GPU (--ranks_share_gpu): 256 co-resident workgroups are not assured
+    if not native_split_ok(sess, cid, mode) or not hasattr(sess.ops.C(), m.executor):
+        return False
+    reason = m.dtype_reason(*_dtypes(sess))
+    if reason is None and not 1 <= sess.B <= 16:
+        # every product's MFMA row block is the batch (csrc/vanilla.hip): larger batches run per batch
+        reason = f"batch {sess.B} > 16: per-batch executor"
+    if reason is not None:
+        sess.split_persist_reason = reason
+        return False
+    return (sess.alices[cid].slot.cfg.kind == m.opt_kind and sess.bob_slot(cid).cfg.kind == m.opt_kind
+            and len(sess.tail.layers) == m.n_layers and all(L.W.dtype == torch.float32 for L in sess.tail.layers))
+
+
+def _shared_cfg(sess) -> dict:
+    return {"B": sess.B, "timeout_s": float(getattr(sess.args, "persist_timeout_s", 30.0)),
+            # a plain (non-cooperative) launch of the same grid for rocprofv3, whose process dies at
+            # exit after any cooperative launch (docs/PERF.md, tools/coop_repro.hip)
+            "workgroups": int(os.environ.get("SL_PERSIST_WORKGROUPS", "0"))}
+
+
+def persist_cfg(sess, cid: int, mode: str) -> dict:
+    """What the co-located persistent executor is built from: Bob's half (the whole cfg of the
+    remote executor's side), the Alice's half and the shared scalars."""
+    m = _MODES[mode]
+    return {**m.alice_cfg(sess, cid), **m.bob_cfg(sess, cid), **_shared_cfg(sess)}
+
+
+def run_persistent_epoch(sess, cid: int, order: torch.Tensor, mode: str) -> bool:
+    """One epoch of a co-located Alice_cid as ONE launch (`_C.VanillaEpoch`, csrc/vanilla.hip;
+    `_C.UShapeEpoch`, csrc/ushape.hip: every parameter and Adam moment of model1 / model2 /
+    model3 on-chip).  Fail-safe: the Alice's and Bob's parameters and optimizer states are
+    copied first; if the launch fails they are restored, the persistent executor is switched
+    off for the session (`split_persist_fallback`) and False is returned, so the caller runs
+    the epoch on the per-batch executor instead."""
+    m = _MODES[mode]
+    cfg = persist_cfg(sess, cid, mode)
+    ex = getattr(sess.ops.C(), m.executor)(cfg)
     if not ex.ok():
-        sess.__dict__["_us_off"] = True
-        sess.__dict__["split_persist_reason"] = ex.why()
+        sess.persist_off = True
+        sess.split_persist_reason = ex.why()
         return False
     a = sess.alices[cid]
     order = order.to(sess.device, torch.int64).contiguous()
-    state = [t for k in ("fc1", "fc2", "conv", "head") for t in cfg[k].values()]
+    state = m.state(cfg)
     snap = [t.clone() for t in state] if getattr(sess.args, "persistent_failsafe", "on") != "off" else None
-    B = sess.B
-    nb = -(-int(order.numel()) // B)
-    loss = torch.empty(max(nb, 1) * B, dtype=torch.float32, device=sess.device)
+    nb = -(-int(order.numel()) // sess.B)
+    loss = _loss_buf(sess, nb)
     sess.tail._pre = None
-    if sess.__dict__.get("_us_max_steps"):
-        ex.set_max_steps(int(sess._us_max_steps))      # tests: the epoch as several launches
-    fault = sess.__dict__.pop("_us_fault_step", None)
+    if sess.persist_max_steps:
+        ex.set_max_steps(int(sess.persist_max_steps))
+    fault, sess.persist_fault_step = sess.persist_fault_step, None
     if fault is not None:
         ex.set_fault_step(int(fault))
     try:
-        t_a, t_b = ex.run(order, loss, a.slot.t, sess.bob_slot(cid).t)
+        t_a, t_b, fc = m.run(ex, sess, cid, order, loss, nb)
     except RuntimeError as e:
         if snap is None:
             raise
         for t, s in zip(state, snap):
             t.copy_(s)
-        sess.__dict__["_us_off"] = True
-        sess.__dict__["split_persist_fallback"] = str(e).splitlines()[0][:200]
+        sess.persist_off = True
+        sess.split_persist_fallback = str(e).splitlines()[0][:200]
         return False
     _count(sess, "persistent")
     a.slot.t = int(t_a)
-    _bob_done(sess, cid, t_b, sess.tail.fwd_count + nb)
-    a.head.fwd_count += nb
-    sess.__dict__["last_split_losses"] = loss[:order.numel()]
+    _bob_done(sess, cid, t_b, fc)
+    if a.head is not None:
+        a.head.fwd_count += nb
+    sess.last_split_losses = loss[:order.numel()]
     return True
 
 
@@ -367,81 +373,40 @@ def persistent_remote_ok(sess, cid: int, mode: str) -> bool:
     dtype; and a GPU of its own: with ranks sharing one GPU the Alice's kernels need CUs the
     launch would hold, so only an explicit reduced grid (SL_VA_REMOTE_G / SL_US_REMOTE_G, the
     one-GPU tests) runs there."""
-    if mode not in ("vanilla", "ushape") or getattr(sess.args, "split_persist", "auto") == "off":
-        return False
-    if sess.__dict__.get("_va_rem_off" if mode == "vanilla" else "_us_rem_off"):
+    m = _MODES.get(mode)
+    if m is None or getattr(sess.args, "split_persist", "auto") == "off" or sess.persist_remote_off:
         return False
     ch = getattr(sess, "split_channel", None)
-    C = sess.ops.C()
-    if ch is None or not hasattr(ch, "host_error") or not hasattr(C, "VanillaEpoch" if mode == "vanilla" else "UShapeEpoch"):
+    if ch is None or not hasattr(ch, "host_error") or not hasattr(sess.ops.C(), m.executor):
         return False
-    if getattr(sess.comm, "host_staging", False) and not os.environ.get("SL_VA_REMOTE_G" if mode == "vanilla" else "SL_US_REMOTE_G"):
+    if getattr(sess.comm, "host_staging", False) and not os.environ.get(m.remote_env):
         return False
-    dt = getattr(sess.args, "dtype", "fp32")
-    cdt = C.get_compute_dtype() if hasattr(C, "get_compute_dtype") else "fp32"
     t = sess.tail
     if not (1 <= sess.B <= 16 and t.tp_size == 1 and all(L.W.dtype == torch.float32 for L in t.layers)):
         return False
-    if mode == "vanilla":
-        return dt == "fp32" and cdt == "fp32" and sess.bob_slot(cid).cfg.kind == "sgd" and len(t.layers) == 3
-    return dt in ("fp32", "bf16") and cdt == dt and sess.bob_slot(cid).cfg.kind == "adam" and len(t.layers) == 2
+    return (m.dtype_reason(*_dtypes(sess)) is None and sess.bob_slot(cid).cfg.kind == m.opt_kind
+            and len(t.layers) == m.n_layers)
 
 
-def _run_remote_persistent_ushape(sess, cid: int, n: int, peer: int):
-    """Bob's half of a remote U-shape epoch as one persistent launch (`_C.UShapeEpoch.run_remote`),
-    as `_run_remote_persistent` for vanilla."""
-    bslot = sess.bob_slot(cid)
-    L1, L2 = sess.tail.layers
-    cfg = {"fc1": _six(bslot, L1.spec.name, L1.W, L1.b), "fc2": _six(bslot, L2.spec.name, L2.W, L2.b),
-           "bob_opt": _adam(bslot.cfg), "B": sess.B,
-           "timeout_s": float(getattr(sess.args, "persist_timeout_s", 30.0)),
-           "channel": sess.split_channel, "peer": int(peer),
-           "G": int(os.environ.get("SL_US_REMOTE_G", "256")),
-           "workgroups": int(os.environ.get("SL_PERSIST_WORKGROUPS", "0")),
-           "bf16": getattr(sess.args, "dtype", "fp32") == "bf16"}
-    ex = sess.ops.C().UShapeEpoch(cfg)
-    if not ex.ok():
-        sess.__dict__["_us_rem_off"] = True
-        sess.__dict__["split_persist_reason"] = "remote: " + ex.why()
-        return None
-    sess.tail._pre = None
-    t_b = ex.run_remote(int(n), bslot.t)
-    _bob_done(sess, cid, t_b, sess.tail.fwd_count + -(-int(n) // sess.B))
-    _count(sess, "remote_persistent")
-    return ex
-
-
-def _run_remote_persistent(sess, cid: int, n: int, peer: int, mode: str = "vanilla"):
-    """Bob's half of a remote vanilla epoch as one persistent launch; None when the executor
-    declines this configuration (the caller then runs run_bob, which Alice cannot tell apart).
-    A launch that fails mid-epoch raises: the Alice is then stopped at a message of this epoch
-    and times out on her side, so there is no state both sides could roll back to (fail-stop,
+def _run_remote_persistent(sess, cid: int, n: int, peer: int, mode: str):
+    """Bob's half of a remote epoch as one persistent launch; None when the executor declines
+    this configuration (the caller then runs run_bob, which Alice cannot tell apart).  A launch
+    that fails mid-epoch raises: the Alice is then stopped at a message of this epoch and times
+    out on her side, so there is no state both sides could roll back to (fail-stop,
     docs/DEVIATIONS.md)."""
-    if mode == "ushape":
-        return _run_remote_persistent_ushape(sess, cid, n, peer)
-    bslot = sess.bob_slot(cid)
-    layers = []
-    for L in sess.tail.layers:
-        pw, pb = _param(bslot, f"{L.spec.name}.weight", L.W), _param(bslot, f"{L.spec.name}.bias", L.b)
-        layers.append({"W": pw["p"], "b": pb["p"], "s0": pw["s0"], "sb0": pb["s0"]})
-    bo = bslot.cfg
-    cfg = {"layers": layers, "lr": bo.lr, "momentum": bo.momentum, "wd": bo.weight_decay, "B": sess.B,
-           "p1": sess.tail.layers[0].spec.dropout, "p2": sess.tail.layers[1].spec.dropout,
-           "timeout_s": float(getattr(sess.args, "persist_timeout_s", 30.0)),
-           "channel": sess.split_channel, "peer": int(peer),
-           "G": int(os.environ.get("SL_VA_REMOTE_G", "256")),
-           "workgroups": int(os.environ.get("SL_PERSIST_WORKGROUPS", "0"))}
-    ex = sess.ops.C().VanillaEpoch(cfg)
+    m = _MODES[mode]
+    cfg = {**m.bob_cfg(sess, cid), **_shared_cfg(sess), "channel": sess.split_channel, "peer": int(peer),
+           "G": int(os.environ.get(m.remote_env, "256"))}
+    ex = getattr(sess.ops.C(), m.executor)(cfg)
     if not ex.ok():
-        sess.__dict__["_va_rem_off"] = True
-        sess.__dict__["split_persist_reason"] = "remote: " + ex.why()
+        sess.persist_remote_off = True
+        sess.split_persist_reason = "remote: " + ex.why()
         return None
-    nb = -(-int(n) // sess.B)
-    loss = torch.empty(max(nb, 1) * sess.B, dtype=torch.float32, device=sess.device)
     sess.tail._pre = None
-    t_b, fc = ex.run_remote(int(n), loss, bslot.t, sess.tail.fwd_count, sess.tail.seed_base)
+    t_b, fc, loss = m.run_remote(ex, sess, cid, int(n), -(-int(n) // sess.B))
     _bob_done(sess, cid, t_b, fc)
-    sess.__dict__["last_split_losses"] = loss[:int(n)]
+    if loss is not None:
+        sess.last_split_losses = loss[:int(n)]
     _count(sess, "remote_persistent")
     return ex
 

@@ -18,15 +18,14 @@ from __future__ import annotations
 import torch
 
 from ..config import CUT_FEATURES
-from ..engine.slots import OptSlot, adam
+from ..engine.slots import adam
 from ..engine.tail import TailEngine
 from ..models import ClientFront, Head, ServerTailUShape, head_spec, ushape_server_spec
-from .base import AliceState, Session, _progress
-from .split_native import (native_remote_role, native_split_ok, persistent_ushape_ok, run_native_remote_epoch,
-                           run_native_split_epoch, run_persistent_ushape_epoch)
+from .base import AliceState
+from .split import SplitSession
 
 
-class UShapeSession(Session):
+class UShapeSession(SplitSession):
     mode = "ushape"
 
     def front_module(self):
@@ -44,12 +43,6 @@ class UShapeSession(Session):
     def _extend_alice(self, a: AliceState):
         torch.manual_seed(self.seed + 2000 + a.cid)
         a.head = TailEngine(Head(), head_spec(), self.device)
-
-    def bob_slot(self, cid: int) -> OptSlot:
-        s = self.bob_slots.get(cid)
-        if s is None:
-            s = self.bob_slots[cid] = OptSlot(self.bob_optim())
-        return s
 
     # ------------------------------------------------------------------ weights (model1 + model3)
     def give_weights(self, cid: int):
@@ -126,116 +119,38 @@ class UShapeSession(Session):
         if a is not None:
             a.front.backward_step(dx, act, am, a.train, idx, a.slot, t=t, prefix="front.")
 
-    def split_epoch(self, cid: int, order, n: int):
-        """U-shape training of Alice_cid over `order` (n samples), pipelined like
-        VanillaSession.split_epoch: per batch i, Bob's forward, the head + CE + head step on
-        Alice, Bob's data gradients, Alice's conv backward + step and her forward of batch
-        i+1 (sent to Bob) — and only then Bob's wgrad + Adam of both layers in one launch,
-        which also forms batch i+1's fc1 product with the updated weights (no separate fc1
-        forward read).  Same per-batch math and update order as `split_step`.  When no Bob
-        shard shares the Alice's GPU (`split_lookahead`), Bob's update is issued right after
-        the cut gradient leaves instead, so it runs during her backward and next forward."""
-        B = self.B
-        a = self.alices.get(cid)
-        host = self.host(cid)
-        spans = [(s, min(s + B, n)) for s in range(0, n, B)]
-        if not spans:
-            return
-        if order is not None and persistent_ushape_ok(self, cid) and run_persistent_ushape_epoch(self, cid, order):
-            return                                # the whole epoch in one launch, state on-chip
-        if order is not None and native_split_ok(self, cid, "ushape"):
-            run_native_split_epoch(self, cid, order, "ushape")   # the same launches, issued from C++
-            return
-        role = native_remote_role(self, cid, "ushape")   # collective over the Alice's and Bob's ranks
-        if role is not None:                      # remote Alice: each side's half from C++
-            run_native_remote_epoch(self, cid, order, n, "ushape", role)
-            return
-        grouped = self.is_bob and self.tail.grouped_ok()
-        la = self.split_lookahead(cid)
+    # ------------------------------------------------------------------ the mode's part of split_epoch
+    def _send_act(self, cid, act, labels, rows):
+        return self.act_to_bob(cid, act, rows), labels      # the labels stay with the Alice
 
-        def alice_fwd(span):
-            s, e = span
-            idx = order[s:e] if order is not None else None
-            act = am = labels = None
-            if a is not None:
-                act, am, labels = a.front.forward(a.train, idx, with_labels=True)
-            return idx, act, am, labels, self.act_to_bob(cid, act, e - s)
-
-        cur = alice_fwd(spans[0])
-        pre = False
-        for i, (s, e) in enumerate(spans):
-            idx, act, am, labels, act_b = cur
-            M = e - s
-            out = self.tail.forward(act_b, train=True, pre=pre) if self.is_bob else None
-            mid = self.from_bob(cid, out, (M, 100))
-            dmid = t = None
-            if a is not None:
-                t = a.slot.tick()
-                dmid = self.head_train(a, mid, labels, t)
-            dmid_b = self.to_bob(cid, dmid, (M, 100))
-            dxp = (self.tail.backward_dgrad(dmid_b, need_dx=True, premasked=self.head_fused(M))
-                   if self.is_bob else None)
-            dx = self.comm.reduce_to(dxp, host, self.bob_ranks, (M, CUT_FEATURES), torch.float32)
-            pre = False
-            if self.is_bob and not la:           # Alice remote from every Bob shard: the
-                if grouped:                      # update overlaps her backward + next forward
-                    self.tail.group_step(self.bob_slot(cid), x_next=None)
-                else:
-                    self.tail.backward_step(self.bob_slot(cid))
-            if a is not None:
-                a.front.backward_step(dx, act, am, a.train, idx, a.slot, t=t, prefix="front.", defer=True)
-            nxt = alice_fwd(spans[i + 1]) if i + 1 < len(spans) else None
-            if self.is_bob and la:
-                if grouped:
-                    x_next = nxt[4] if (la and nxt is not None and self.tail.grouped_ok(nxt[4].shape[0])) else None
-                    self.tail.group_step(self.bob_slot(cid), x_next=x_next)
-                    pre = x_next is not None
-                else:
-                    self.tail.backward_step(self.bob_slot(cid))
-            cur = nxt
+    def _bob_middle(self, cid, a, act_b, labels, M, pre):
+        """Bob's forward, the head + CE + head step on Alice, Bob's data gradients: the partial
+        cut gradient and the Alice's step count `t`, which her conv update shares."""
+        out = self.tail.forward(act_b, train=True, pre=pre) if self.is_bob else None
+        mid = self.from_bob(cid, out, (M, 100))
+        dmid = t = None
         if a is not None:
-            a.front.flush()          # the last step's deferred client update
+            t = a.slot.tick()
+            dmid = self.head_train(a, mid, labels, t)
+        dmid_b = self.to_bob(cid, dmid, (M, 100))
+        dxp = (self.tail.backward_dgrad(dmid_b, need_dx=True, premasked=self.head_fused(M))
+               if self.is_bob else None)
+        return dxp, t
 
-    def _run_epochs(self, cid: int, order_fn, n: int):
-        for _ in _progress(range(self.args.epochs), self.show, desc="Epochs", ascii=" >="):
-            a = self.alices.get(cid)
-            order = order_fn(a) if a is not None else None
-            self.split_epoch(cid, order, n)
+    def _bob_updater(self, cid, ahead):
+        """Bob's wgrad + Adam, of both layers in one launch when grouped; in the look-ahead order
+        that launch also forms the next batch's fc1 product when `grouped_ok` for its rows."""
+        grouped = self.tail.grouped_ok()
 
-    # ------------------------------------------------------------------ Bob API
-    def train_request(self, client_id: int):
-        self.bob_log.info(f"Train Request for Alice-{client_id}")
-        a = self.alices.get(client_id)
-        if a is not None:
-            a.logger.info("Training")
-            if self.last_alice_id is None:
-                a.logger.info(f"Alice-{client_id} is first client to train")
-            else:
-                a.logger.info(f"Alice-{client_id} receiving weights from Alice-{self.last_alice_id}")
-        if self.last_alice_id is not None:
-            self.relay_weights(self.last_alice_id, client_id)
-        self._run_epochs(client_id, lambda al: al.train.shuffled_order(al.gen), self.n_train[client_id])
-        self.last_alice_id = client_id
-
-    def unlearn_request(self, client_id: int, omit_label: int):
-        """U-shape unlearning (absent in the reference, Q1): reset + fresh Adam states
-        (client and Bob-side slot) + retrain on the filtered shard."""
-        self.bob_log.info(f"Unlearn Request for Alice-{client_id}")
-        a = self.alices.get(client_id)
-        order = None
-        if a is not None:
-            a.logger.info("Retraining")
-            self.reset_model(client_id)
-            a.slot = OptSlot(self.alice_optim())
-            order = self.filtered_order(a, omit_label)
-            a.unlearn_order = order
-            a.logger.info("Retraining dataset: {}".format(self.label_counter(a, order)))
-            a.logger.info("Test dataset (retraining): {}".format(a.test.label_counter()))
-        self.bob_slots[client_id] = OptSlot(self.bob_optim())
-        n = torch.tensor([order.numel() if order is not None else 0], dtype=torch.int64, device=self.device)
-        n = int(self.comm.multicast(n if a is not None else None, self.host(client_id),
-                                    range(self.comm.world), (1,), torch.int64).item())
-        self._run_epochs(client_id, lambda al: al.unlearn_order, n)
+        def update(x_next):
+            if not grouped:
+                self.tail.backward_step(self.bob_slot(cid))
+                return False
+            if x_next is not None and not self.tail.grouped_ok(x_next.shape[0]):
+                x_next = None
+            self.tail.group_step(self.bob_slot(cid), x_next=x_next)
+            return x_next is not None
+        return update
 
     # ------------------------------------------------------------------ eval hooks
     def bob_out_width(self) -> int:

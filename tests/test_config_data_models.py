@@ -251,7 +251,7 @@ def test_split_persist_flag_and_cpu_decision(tmp_path):
     from splitlearning_amd.data.mnist import write_shards
     from splitlearning_amd.parallel.dist import Comm, Placement
     from splitlearning_amd.protocols import VanillaSession
-    from splitlearning_amd.protocols.split_native import persistent_vanilla_ok
+    from splitlearning_amd.protocols.split_native import persistent_ok
     assert parse_args(["--vanilla"]).split_persist == "auto"
     assert parse_args(["--vanilla", "--split_persist", "off"]).split_persist == "off"
     args = parse_args(["--vanilla", "--world_size", "2", "--num_samples", "300", "--no_tqdm",
@@ -259,7 +259,7 @@ def test_split_persist_flag_and_cpu_decision(tmp_path):
     write_shards(args, verbose=False)
     dev = torch.device("cpu")
     s = VanillaSession(args, Comm(0, 1, dev, Placement.make(2, 1, 1)), dev)
-    assert not persistent_vanilla_ok(s, 1)
+    assert not persistent_ok(s, 1, "vanilla")
 
 
 def test_split_persist_batch_bound_is_reported(tmp_path, monkeypatch):
@@ -289,7 +289,7 @@ def test_split_persist_batch_bound_is_reported(tmp_path, monkeypatch):
     dev = torch.device("cpu")
     s = VanillaSession(args, Comm(0, 1, dev, Placement.make(2, 1, 1)), dev)
     s.ops = _Ops()
-    assert not split_native.persistent_vanilla_ok(s, 1)
+    assert not split_native.persistent_ok(s, 1, "vanilla")
     assert "batch 32 > 16" in s.split_persist_reason
 
 
@@ -329,7 +329,7 @@ def test_persistent_vanilla_refuses_bf16(tmp_path, monkeypatch):
         dev = torch.device("cpu")
         s = VanillaSession(args, Comm(0, 1, dev, Placement.make(2, 1, 1)), dev)
         s.ops = _Ops(dt)
-        assert split_native.persistent_vanilla_ok(s, 1) is want, (flag, dt)
+        assert split_native.persistent_ok(s, 1, "vanilla") is want, (flag, dt)
         if not want:
             assert "bf16" in s.__dict__.get("split_persist_reason", "")
 
@@ -387,7 +387,7 @@ def test_persistent_remote_vanilla_decision(tmp_path, monkeypatch):
     assert not split_native.persistent_remote_ok(s, 1, "vanilla")
     monkeypatch.setenv("SL_VA_REMOTE_G", "64")
     assert split_native.persistent_remote_ok(s, 1, "vanilla")
-    s._va_rem_off = True                  # an earlier decline in this session
+    s.persist_remote_off = True           # an earlier decline in this session
     assert not split_native.persistent_remote_ok(s, 1, "vanilla")
 
 

@@ -124,7 +124,7 @@ def test_vanilla_epoch_long_launch(cuda, tmp_path):
     sc = _session("vanilla", tmp_path, True, cuda, B)
     with torch.no_grad():                         # the control: Bob's fc1 moved by one ulp
         sc.tail.layers[0].W.copy_(_ulp(sc.tail.layers[0].W))
-    s2._va_max_steps = CHUNK
+    s2.persist_max_steps = CHUNK
     tr = s1.alices[1].train
     reps = -(-(STEPS * B + 7) // len(tr.y))
     order = torch.cat([tr.shuffled_order(torch.Generator().manual_seed(40 + r)) for r in range(reps)])

@@ -44,10 +44,10 @@ def _epochs(s, order, B):
 
 @pytest.mark.parametrize("B", [16, 5])
 def test_persistent_ushape_matches_per_batch(cuda, tmp_path, B):
-    from splitlearning_amd.protocols.split_native import persistent_ushape_ok
+    from splitlearning_amd.protocols.split_native import persistent_ok
     sp = _session("ushape", tmp_path, True, cuda, B)
     sq = _session("ushape", tmp_path, True, cuda, B, persist=True)
-    assert persistent_ushape_ok(sq, 1) and not persistent_ushape_ok(sp, 1)
+    assert persistent_ok(sq, 1, "ushape") and not persistent_ok(sp, 1, "ushape")
     order = sp.alices[1].train.shuffled_order(torch.Generator().manual_seed(4))[:B * 6 + 3].to(cuda)
     for s in (sp, sq):
         _epochs(s, order, B)
@@ -64,7 +64,7 @@ def test_persistent_ushape_one_launch_is_bitwise_step_launches(cuda, tmp_path):
     s1 = _session("ushape", tmp_path, True, cuda, B, persist=True)
     s2 = _session("ushape", tmp_path, True, cuda, B, persist=True)
     s3 = _session("ushape", tmp_path, True, cuda, B, persist=True)
-    s3._us_max_steps = 2          # the executor's own chunking: launches of at most 2 steps
+    s3.persist_max_steps = 2          # the executor's own chunking: launches of at most 2 steps
     order = s1.alices[1].train.shuffled_order(torch.Generator().manual_seed(7))[:B * 5 + 7].to(cuda)
     s1.split_epoch(1, order, order.numel())
     s3.split_epoch(1, order, order.numel())
@@ -88,7 +88,7 @@ def test_persistent_ushape_mid_epoch_failure_falls_back(cuda, tmp_path):
     sq = _session("ushape", tmp_path, True, cuda, B, persist=True)
     sq.args.persist_timeout_s = 0.5
     order = sp.alices[1].train.shuffled_order(torch.Generator().manual_seed(5))[:B * 6].to(cuda)
-    sq._us_fault_step = 3
+    sq.persist_fault_step = 3
     for s in (sp, sq):
         s.split_epoch(1, order, order.numel())
     torch.cuda.synchronize()
@@ -103,7 +103,7 @@ def test_persistent_ushape_long_launch_is_bitwise_chunks(cuda, tmp_path):
     B, steps = 16, 1000
     s1 = _session("ushape", tmp_path, True, cuda, B, persist=True)
     s2 = _session("ushape", tmp_path, True, cuda, B, persist=True)
-    s2._us_max_steps = 100
+    s2.persist_max_steps = 100
     tr = s1.alices[1].train
     reps = -(-(steps * B + 7) // len(tr.y))
     order = torch.cat([tr.shuffled_order(torch.Generator().manual_seed(60 + r)) for r in range(reps)])
@@ -137,14 +137,14 @@ def test_persistent_ushape_bf16_matches_per_batch_bf16(cuda, tmp_path):
     bf16 executor within the Adam bound, differs from the fp32 persistent epoch (the bf16
     products really ran), and one launch is bitwise its one-step launches."""
     from splitlearning_amd.ops import hip_ops
-    from splitlearning_amd.protocols.split_native import persistent_ushape_ok
+    from splitlearning_amd.protocols.split_native import persistent_ok
     B = 16
     try:
         sp = _session_bf16(tmp_path, cuda, False)
         sq = _session_bf16(tmp_path, cuda, True)
         s1 = _session_bf16(tmp_path, cuda, True)
         assert hip_ops.C().get_compute_dtype() == "bf16"
-        assert persistent_ushape_ok(sq, 1) and not persistent_ushape_ok(sp, 1)
+        assert persistent_ok(sq, 1, "ushape") and not persistent_ok(sp, 1, "ushape")
         order = sp.alices[1].train.shuffled_order(torch.Generator().manual_seed(4))[:B * 6 + 3].to(cuda)
         for s in (sp, sq):
             _epochs(s, order, B)

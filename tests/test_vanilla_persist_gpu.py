@@ -34,10 +34,10 @@ def _epochs(s, order, B):
 
 @pytest.mark.parametrize("B", [16, 5])
 def test_persistent_vanilla_matches_per_batch(cuda, tmp_path, B):
-    from splitlearning_amd.protocols.split_native import persistent_vanilla_ok
+    from splitlearning_amd.protocols.split_native import persistent_ok
     sp = _session("vanilla", tmp_path, True, cuda, B)
     sq = _session("vanilla", tmp_path, True, cuda, B, persist=True)
-    assert persistent_vanilla_ok(sq, 1) and not persistent_vanilla_ok(sp, 1)
+    assert persistent_ok(sq, 1, "vanilla") and not persistent_ok(sp, 1, "vanilla")
     order = sp.alices[1].train.shuffled_order(torch.Generator().manual_seed(4))[:B * 6 + 3].to(cuda)
     for s in (sp, sq):
         _epochs(s, order, B)
@@ -53,7 +53,7 @@ def test_persistent_vanilla_one_launch_is_bitwise_step_launches(cuda, tmp_path):
     s1 = _session("vanilla", tmp_path, True, cuda, B, persist=True)
     s2 = _session("vanilla", tmp_path, True, cuda, B, persist=True)
     s3 = _session("vanilla", tmp_path, True, cuda, B, persist=True)
-    s3._va_max_steps = 2          # the executor's own chunking: launches of at most 2 steps
+    s3.persist_max_steps = 2          # the executor's own chunking: launches of at most 2 steps
     order = s1.alices[1].train.shuffled_order(torch.Generator().manual_seed(7))[:B * 5 + 7].to(cuda)
     s1.split_epoch(1, order, order.numel())
     s3.split_epoch(1, order, order.numel())
@@ -77,7 +77,7 @@ def test_persistent_vanilla_mid_epoch_failure_falls_back(cuda, tmp_path):
     sq = _session("vanilla", tmp_path, True, cuda, B, persist=True)
     sq.args.persist_timeout_s = 0.5
     order = sp.alices[1].train.shuffled_order(torch.Generator().manual_seed(5))[:B * 6].to(cuda)
-    sq._va_fault_step = 3
+    sq.persist_fault_step = 3
     for s in (sp, sq):
         s.split_epoch(1, order, order.numel())
     torch.cuda.synchronize()
@@ -93,9 +93,9 @@ def test_persistent_vanilla_update_runs_partition_the_tiles(cuda, tmp_path):
     order (the dx partials' sum order, as when runs were dealt in order), and the runs are dealt
     to workgroups by the row band they start in (workgroup w on XCD w % 8 stages ~1/4 of the row
     blocks' dz1, not all of them)."""
-    from splitlearning_amd.protocols.split_native import _va_cfg
+    from splitlearning_amd.protocols.split_native import persist_cfg
     s = _session("vanilla", tmp_path, True, cuda, 16, persist=True)
-    ex = s.ops.C().VanillaEpoch(_va_cfg(s, 1))
+    ex = s.ops.C().VanillaEpoch(persist_cfg(s, 1, "vanilla"))
     assert ex.ok(), ex.why()
     G = ex.workgroups()
     tab = ex.table().cpu().tolist()
