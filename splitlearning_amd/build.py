@@ -1,12 +1,14 @@
 """In-tree native build: compile the gfx950 HIP kernels + bindings into
-`splitlearning_amd/_C<ext>.so` with hipcc (no hipify, no JIT cache).
+`splitlearning_amd/_C<ext>.so` and `splitlearning_amd/_C2<ext>.so` with hipcc (no hipify, no JIT
+cache).  `_C`'s surface is pinned (tests/data/native_surface.json); kernel families added since
+live in `_C2`, which links torch and amdhip64 only.
 
     python -m splitlearning_amd.build          # incremental
     python -m splitlearning_amd.build --force  # rebuild everything
 
-Objects go to `splitlearning_amd/build/` (git-ignored); the `.so` lands next to
-this file so `gpurun` snapshots carry it to the GPU box.  Cross-compiles fine on
-a host without a GPU.
+Objects go to `splitlearning_amd/build/` (git-ignored); the `.so` files land next to
+this file, so the package imports from the tree.  Cross-compiles fine on a host
+without a GPU.
 """
 from __future__ import annotations
 
@@ -25,13 +27,18 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 KERNEL_SOURCES = ["conv.hip", "linear.hip", "loss.hip", "fused.hip", "gemm.hip", "ipc_ar.hip", "ipc_p2p.hip", "resident.hip", "hybrid.hip", "vanilla.hip", "handoff.hip", "ushape.hip", "optim.hip", "conv2d.hip", "groupnorm.hip", "cutcodec.hip"]
 BINDING_SOURCES = ["bindings.cpp", "comm.cpp", "engine.cpp", "split.cpp", "resident_exec.cpp", "hybrid_exec.cpp", "vanilla_exec.cpp", "ushape_exec.cpp", "handoff_exec.cpp"]
+KERNEL_SOURCES2 = ["cuttopk.hip"]
+BINDING_SOURCES2 = ["bindings2.cpp"]
+# module name -> (kernel sources, binding sources, libraries beyond torch and amdhip64)
+MODULES = {"_C": (KERNEL_SOURCES, BINDING_SOURCES, ["-lrccl"]),
+           "_C2": (KERNEL_SOURCES2, BINDING_SOURCES2, [])}
 
 
-def so_path() -> str:
-    return os.path.join(HERE, "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
+def so_path(module: str = "_C") -> str:
+    return os.path.join(HERE, module + sysconfig.get_config_var("EXT_SUFFIX"))
 
 
-def _torch_flags():
+def _torch_flags(module: str, libs: list[str]):
     import torch
     from torch.utils import cpp_extension as ce
     inc = ce.include_paths()
@@ -40,9 +47,9 @@ def _torch_flags():
     cflags = [f"-I{p}" for p in inc] + [f"-I{sysconfig.get_paths()['include']}",
                                         f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
                                         "-DTORCH_API_INCLUDE_EXTENSION_H",
-                                        "-DTORCH_EXTENSION_NAME=_C", "-DUSE_ROCM=1"]
+                                        f"-DTORCH_EXTENSION_NAME={module}", "-DUSE_ROCM=1"]
     ldflags = [f"-L{tlib}", "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip",
-               "-ltorch_python", "-lamdhip64", "-lrccl", f"-Wl,-rpath,{tlib}"]
+               "-ltorch_python", "-lamdhip64"] + libs + [f"-Wl,-rpath,{tlib}"]
     return cflags, ldflags
 
 
@@ -68,14 +75,14 @@ def _compile(src: str, extra: list[str], force: bool) -> str:
     return obj
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
-    os.makedirs(OBJ, exist_ok=True)
-    cflags, ldflags = _torch_flags()
-    jobs = [(os.path.join(CSRC, s), []) for s in KERNEL_SOURCES]
-    jobs += [(os.path.join(CSRC, s), cflags) for s in BINDING_SOURCES]
+def _build_module(module: str, force: bool, verbose: bool) -> str:
+    kernels, bindings, libs = MODULES[module]
+    cflags, ldflags = _torch_flags(module, libs)
+    jobs = [(os.path.join(CSRC, s), []) for s in kernels]
+    jobs += [(os.path.join(CSRC, s), cflags) for s in bindings]
     with ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
         objs = list(ex.map(lambda j: _compile(j[0], j[1], force), jobs))
-    out = so_path()
+    out = so_path(module)
     if force or not os.path.exists(out) or any(os.path.getmtime(o) > os.path.getmtime(out) for o in objs):
         cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out] + objs + ldflags
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -84,6 +91,13 @@ def build(force: bool = False, verbose: bool = True) -> str:
     if verbose:
         print(f"[splitlearning_amd.build] {out}")
     return out
+
+
+def build(force: bool = False, verbose: bool = True) -> str:
+    """Build `_C`, then `_C2`; returns `_C`'s path."""
+    os.makedirs(OBJ, exist_ok=True)
+    outs = [_build_module(m, force, verbose) for m in MODULES]
+    return outs[0]
 
 
 def main(argv=None):

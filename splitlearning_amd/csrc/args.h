@@ -51,7 +51,8 @@ inline void need_rows(const at::Tensor& t, const char* name) {
 // it with 32-bit byte offsets
 inline void need_dense(const at::Tensor& t, at::ScalarType ty, const char* name, bool under_2gb = false) {
   need_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == ty, name, " must be ", ty == at::kFloat ? "float32" : ty == at::kByte ? "uint8" : "int8");
+  TORCH_CHECK(t.scalar_type() == ty, name, " must be ",
+              ty == at::kFloat ? "float32" : ty == at::kByte ? "uint8" : ty == at::kInt ? "int32" : "int8");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(t.get_device() == c10::hip::current_device(), name, " must be on the current device");
   if (under_2gb) TORCH_CHECK(t.numel() * (int64_t)t.element_size() < (int64_t(1) << 31), name, " must be under 2 GB");

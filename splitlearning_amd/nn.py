@@ -26,6 +26,12 @@ gradient-norm clipping), and any `torch.optim` optimizer works too:
   scale per group of a row: the activation to the nearest step, its gradient with stochastic
   (unbiased) rounding, one streaming kernel each.  `cut_pack` / `cut_unpack` produce and read the
   wire tensors (`CutPacket`) for a transport.  No parameters and no buffers.
+* `CutTopK`: the cut, sparsified.  Only the k largest-magnitude entries of each sample cross it
+  (ties at the threshold: the lowest positions, so runs repeat bit for bit) and the gradient comes
+  back on the same support: one radix-select kernel forward, one masking kernel backward.
+  `cut_sparsify` / `cut_densify` / `cut_sparse_grad` produce and read the wire tensors
+  (`CutSparsePacket`: values + int32 positions); the values are an ordinary tensor that `cut_pack`
+  quantises further.  No parameters and no buffers.
 
 On CPU tensors the same layers run the eager torch implementations (ops/torch_ops.py),
 so a model is written once. State-dict keys match `nn.Linear` / `nn.Conv2d` / `nn.GroupNorm` /
@@ -417,5 +423,116 @@ def cut_unpack(packet: CutPacket) -> torch.Tensor:
     return y.view(packet.shape)
 
 
+# ------------------------------------------------------------------ the cut, sparsified
+def _topk_k(name, k, K: int) -> int:
+    if k > K:
+        raise ValueError(f"{name}: k = {k} exceeds the {K} elements of a sample")
+    return k
+
+
+class _TopKFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, k: int, grad_mask: bool):
+        y, indices = ops.impl(x.device).cut_topk_dense(x.reshape(x.shape[0], -1), k)
+        ctx.indices = indices if grad_mask else None
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.indices is None:
+            return dy, None, None
+        dx = ops.impl(dy.device).cut_mask(dy.reshape(dy.shape[0], -1), ctx.indices)
+        return dx.view(dy.shape), None, None
+
+
+class CutTopK(nn.Module):
+    """The cut of a split model, sparsified: only the `k` entries of largest magnitude of each
+    sample cross it, and the other side sees zeros elsewhere.
+
+    x [B, *] float32 is read as [B, K].  A sample's support is the k columns with the largest |x|;
+    among equal magnitudes at the threshold the lowest columns win, so a run repeats bit for bit
+    on every backend.  On the wire that is k values + k int32 positions, 8 k / K bytes per element
+    against 4 (`cut_sparsify`); the values are an ordinary [B, k] tensor, so `cut_pack` quantises
+    them further.  Give exactly one of `k` (an int >= 1) and `ratio` (in (0, 1]: k = max(1,
+    ceil(ratio * K)) for the K of each call).
+
+    Forward: y = x on the support and 0 elsewhere, one kernel; the same in `train()` and `eval()`,
+    since the wire is there at inference too.  Backward: dx = dy on the support and 0 elsewhere, one
+    kernel (what comes back over the wire is `dy` at the k positions, `cut_sparse_grad`);
+    `grad_mask=False` passes the gradient through.  No parameters and no buffers, so state dicts,
+    weight relay, snapshots and unlearning carry a model that contains it unchanged."""
+
+    def __init__(self, k=None, ratio=None, grad_mask: bool = True):
+        super().__init__()
+        if (k is None) == (ratio is None):
+            raise ValueError("CutTopK: give exactly one of k and ratio")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
+            raise ValueError(f"CutTopK: k must be an int >= 1, got {k!r}")
+        if ratio is not None and (isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0 < ratio <= 1):
+            raise ValueError(f"CutTopK: ratio must be in (0, 1], got {ratio!r}")
+        self.k, self.ratio, self.grad_mask = k, ratio, bool(grad_mask)
+
+    def k_for(self, K: int) -> int:
+        """The k of a sample of K elements."""
+        if self.k is not None:
+            return _topk_k("CutTopK", self.k, K)
+        return max(1, math.ceil(self.ratio * K))
+
+    def forward(self, x):
+        _cut_input("CutTopK", x)
+        return _TopKFn.apply(x, self.k_for(math.prod(x.shape[1:])), self.grad_mask)
+
+    def extra_repr(self):
+        return (f"k={self.k}" if self.k is not None else f"ratio={self.ratio}") + f", grad_mask={self.grad_mask}"
+
+
+@dataclass
+class CutSparsePacket:
+    """What `cut_sparsify` makes and a transport ships: `values` (fp32 [B, k]) and `indices` (int32
+    [B, k], ascending in a row: positions in the flattened sample), with the `shape` of the tensor
+    they came from."""
+    values: torch.Tensor
+    indices: torch.Tensor
+    shape: tuple
+    k: int
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors())
+
+    def tensors(self):
+        return self.values, self.indices
+
+
+def cut_sparsify(x, k: int) -> CutSparsePacket:
+    """The k largest-magnitude entries of each sample of x [B, *] float32, for the wire.  Not
+    differentiable: inside a model use `CutTopK`."""
+    _cut_input("cut_sparsify", x)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"cut_sparsify: k must be an int >= 1, got {k!r}")
+    x = x.detach()
+    x2d = x.reshape(x.shape[0], -1)
+    values, indices = ops.impl(x.device).cut_topk(x2d, _topk_k("cut_sparsify", k, x2d.shape[1]))
+    return CutSparsePacket(values, indices, tuple(x.shape), k)
+
+
+def cut_densify(packet: CutSparsePacket) -> torch.Tensor:
+    """The float32 tensor of `packet.shape` the packet stands for: zeros off the support."""
+    K = math.prod(packet.shape[1:])
+    values = packet.values.detach()
+    return ops.impl(values.device).cut_scatter(values, packet.indices, K).view(packet.shape)
+
+
+def cut_sparse_grad(dy, packet: CutSparsePacket) -> torch.Tensor:
+    """The return message: dy [B, *] at the packet's positions, fp32 [B, k].  The side that made
+    the packet holds the indices, and `cut_densify` of these values is its gradient."""
+    _cut_input("cut_sparse_grad", dy)
+    if tuple(dy.shape) != tuple(packet.shape):
+        raise ValueError(f"cut_sparse_grad: dy is {tuple(dy.shape)}, the packet's tensor {tuple(packet.shape)}")
+    dy = dy.detach()
+    return ops.impl(dy.device).cut_gather(dy.reshape(dy.shape[0], -1), packet.indices)
+
+
 __all__ = ["FusedLinear", "FusedConv2d", "FusedGroupNorm", "FusedConvFront", "softmax_cross_entropy", "CutCodec",
-           "CutPacket", "cut_pack", "cut_unpack"]
+           "CutPacket", "cut_pack", "cut_unpack", "CutTopK", "CutSparsePacket", "cut_sparsify", "cut_densify",
+           "cut_sparse_grad"]

@@ -285,6 +285,69 @@ def cut_roundtrip(x2d, bits: int, group: int, seed=None):
     return y
 
 
+# ---------------------------------------------------------------- cut sparsifier
+# csrc/cuttopk.hip (in `_C2`): per-row magnitude top-k of the tensor that crosses the cut, one
+# kernel per call, bitwise equal to ops/torch_ops.py (the definition).  csrc/cuttopk.h's
+# kCutTopkLdsFloats: the longest row the selection keeps in LDS (checked against the extension on
+# first use; tests put shapes on both sides of it).
+CUT_TOPK_LDS_FLOATS = 16000
+_C2_CHECKED = False
+
+
+def C2():
+    global _C2_CHECKED
+    c = _native.load2()
+    if not _C2_CHECKED:
+        if c.cut_topk_lds_floats != CUT_TOPK_LDS_FLOATS:
+            raise RuntimeError("hip_ops.CUT_TOPK_LDS_FLOATS differs from csrc/cuttopk.h")
+        _C2_CHECKED = True
+    return c
+
+
+def _topk_wire(x2d, k: int):
+    R = x2d.shape[0]
+    return (torch.empty(R, int(k), device=x2d.device, dtype=torch.float32),
+            torch.empty(R, int(k), device=x2d.device, dtype=torch.int32))
+
+
+def cut_topk(x2d, k: int):
+    """(values fp32 [R, k], indices int32 [R, k] ascending): the k largest |x| of each row."""
+    x2d = x2d.contiguous()
+    values, indices = _topk_wire(x2d, k)
+    C2().cut_topk(x2d, values, indices)
+    return values, indices
+
+
+def cut_topk_dense(x2d, k: int):
+    """(y, indices) with y = x2d on the support and 0 elsewhere: x is read once and y written once."""
+    x2d = x2d.contiguous()
+    values, indices = _topk_wire(x2d, k)
+    y = torch.empty_like(x2d)
+    C2().cut_topk_dense(x2d, y, values, indices)
+    return y, indices
+
+
+def cut_scatter(values, indices, K: int):
+    y = torch.empty(values.shape[0], int(K), device=values.device, dtype=torch.float32)
+    C2().cut_scatter(values.contiguous(), indices.contiguous(), y)
+    return y
+
+
+def cut_gather(d2d, indices):
+    d2d = d2d.contiguous()
+    values = torch.empty(indices.shape, device=d2d.device, dtype=torch.float32)
+    C2().cut_gather(d2d, indices.contiguous(), values)
+    return values
+
+
+def cut_mask(d2d, indices):
+    """d2d on the support, 0 elsewhere, in one launch."""
+    d2d = d2d.contiguous()
+    dx = torch.empty_like(d2d)
+    C2().cut_mask(d2d, indices.contiguous(), dx)
+    return dx
+
+
 # ---------------------------------------------------------------- linear
 # training batches (M <= 128) run the skinny split-K kernels.  Many rows (evaluation over a
 # test set, large batches): the forward product runs the in-tree LDS-tiled MFMA GEMM

@@ -224,6 +224,52 @@ def cut_roundtrip(x2d, bits: int, group: int, seed=None):
     return cut_unpack(payload, scales, x2d.shape[1], bits, group)
 
 
+# ---------------------------------------------------------------- cut sparsifier
+# The definition of the top-k form of the cut (nn.CutTopK / cut_sparsify / cut_densify /
+# cut_sparse_grad).  x [R, K] fp32, 1 <= k <= K.  The key of an element is |x| (so -0.0 and 0.0 are
+# equal); a row's support is the k columns with the largest keys, and among equal keys at the
+# threshold the lowest columns win: a stable descending sort keeps equal keys in column order, so
+# its first k entries are exactly that.  The wire is values fp32 [R, k] (signs kept) + indices int32
+# [R, k], ascending in a row.  The gradient is dy on the support and 0 elsewhere.
+def _topk_check(x2d, k):
+    if x2d.dim() != 2:
+        raise ValueError(f"cut top-k: expected a 2-D tensor, got {tuple(x2d.shape)}")
+    if x2d.dtype != torch.float32:
+        raise ValueError(f"cut top-k: input must be float32, got {x2d.dtype}")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= x2d.shape[1]:
+        raise ValueError(f"cut top-k: need an integer 1 <= k <= K = {x2d.shape[1]}, got {k!r}")
+
+
+def cut_topk(x2d, k: int):
+    """(values fp32 [R, k], indices int32 [R, k] ascending): the k largest |x| of each row."""
+    _topk_check(x2d, k)
+    order = torch.sort(x2d.abs(), dim=1, descending=True, stable=True).indices[:, :k]
+    idx = order.sort(dim=1).values
+    return x2d.gather(1, idx), idx.to(torch.int32)
+
+
+def cut_scatter(values, indices, K: int):
+    """y [R, K]: 0 everywhere but y[r, indices[r, j]] = values[r, j]."""
+    y = torch.zeros(values.shape[0], K, device=values.device, dtype=values.dtype)
+    return y.scatter_(1, indices.to(torch.int64), values)
+
+
+def cut_gather(d2d, indices):
+    """[R, k]: d2d at the support, the wire form of the gradient."""
+    return d2d.gather(1, indices.to(torch.int64))
+
+
+def cut_topk_dense(x2d, k: int):
+    """(y, indices): what the other side holds after densifying the packet of x2d."""
+    values, indices = cut_topk(x2d, k)
+    return cut_scatter(values, indices, x2d.shape[1]), indices
+
+
+def cut_mask(d2d, indices):
+    """d2d on the support, 0 elsewhere."""
+    return cut_scatter(cut_gather(d2d, indices), indices, d2d.shape[1])
+
+
 # ---------------------------------------------------------------- linear
 # `--dtype bf16`: GEMM operands rounded to bf16, fp32 accumulation (the HIP kernels' rule,
 # csrc/common.h bfr); parameters and optimizer state stay fp32
